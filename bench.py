@@ -24,7 +24,11 @@ against ~1.7 ms launches -- stated in the JSON line as roofline.instrumentation)
 timed steps and ON only in one extra profiled step, which is where roofline_distance_kernel / roofline_encoder /
 encoder_kernels_profiled_step come from.
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  Such a plain run sets up, warms up, times
+the K steps and prints the line (value, ms_per_step, recall@10 of the timed steps, the dominant kernel's roofline from the timed
+region); everything else this script measures or checks (ef sweep, stored-embedding roofline, box probe, memo-off steps, profiled
+step, extra steps, latency rows, parity check, CPU baseline) runs with `--full`.  `--dump-outputs DIR` writes what the last timed
+step returned (DIR/distances.npy, DIR/labels.npy); with the same arguments the inputs are the same in every run.
 For N > 1 the driver launches one rank per GPU through torch.distributed.run; the graph and the
 token store are replicated, the query batch is partitioned across ranks, there is no collective on
 the data path (weak scaling: B queries per rank per step).
@@ -48,6 +52,134 @@ import numpy as np  # noqa: E402
 def log(*a):
     if int(os.environ.get("RANK", "0")) == 0:
         print("[bench]", *a, file=sys.stderr, flush=True)
+
+
+CORPUS_BLOCK = 65536  # SyntheticCorpus.chunks()'s block: one generator per block, seeded [seed, 1, first chunk of the block]
+
+
+def _corpus_block(corpus, b0):
+    """Block `b0` of SyntheticCorpus.chunks(), with the same generator: (tokens, offsets relative to the block)."""
+    s = corpus.spec
+    b1 = min(s.n_chunks, b0 + CORPUS_BLOCK)
+    return corpus._make(np.arange(b0, b1, dtype=np.int64) // s.chunks_per_doc, np.random.default_rng([s.seed, 1, b0]))
+
+
+def _host_cores():
+    """CPUs this process may use: affinity mask, cgroup quota and OMP_NUM_THREADS, shared by the ranks of this node."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    try:
+        q, p_ = open("/sys/fs/cgroup/cpu.max").read().split()
+        if q != "max":
+            n = min(n, max(1, int(q) // int(p_)))
+    except (OSError, ValueError):
+        pass
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit():
+        n = min(n, max(1, int(os.environ["OMP_NUM_THREADS"])))
+    return max(1, n // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
+
+
+class _HostCorpus:
+    """The numpy corpus (SyntheticCorpus.chunks(), block by block) and the queries (SyntheticCorpus.queries()) computed by worker processes
+    that are forked before torch is imported, while the caller goes on with its own set-up.  The bits are those of the serial calls."""
+
+    def __init__(self, corpus, n_queries, skip_chunks=False):
+        self.corpus, self.n_queries = corpus, n_queries
+        self.starts = [] if skip_chunks else list(range(0, corpus.spec.n_chunks, CORPUS_BLOCK))
+        self.pool = None
+        workers = min(len(self.starts) + 1, _host_cores())
+        if len(self.starts) > 1 and workers > 1:
+            import multiprocessing as mp
+            from concurrent.futures import ProcessPoolExecutor
+
+            self.pool = ProcessPoolExecutor(workers, mp_context=mp.get_context("fork"))
+            self.fb = [self.pool.submit(_corpus_block, corpus, b0) for b0 in self.starts]
+            self.fq = self.pool.submit(corpus.queries, n_queries, 4321)  # (needed after the graph build: last)
+
+    def chunks(self):
+        """(tokens u16[total], offsets u64[n+1]), as SyntheticCorpus.chunks() returns them."""
+        parts = [f.result() for f in self.fb] if self.pool else [_corpus_block(self.corpus, b0) for b0 in self.starts]
+        toks, offs, base = [], [np.zeros(1, np.uint64)], 0
+        for t, o in parts:
+            toks.append(t)
+            offs.append(o[1:] + np.uint64(base))
+            base += int(o[-1])
+        return np.concatenate(toks), np.concatenate(offs)
+
+    def queries(self):
+        if self.pool is None:
+            return self.corpus.queries(self.n_queries, seed=4321)
+        q = self.fq.result()
+        self.pool.shutdown()
+        return q
+
+
+class _GroundTruth:
+    """exact_topk_ip(Q, X, k) indices, 256 query rows per call (its own block size: the same results), computed by a thread on a stream of
+    its own -- the graph build that runs meanwhile is mostly host work -- with one block in flight, so that a device-wide synchronisation
+    of the build waits for one block at most."""
+
+    def __init__(self, Q, X, k):
+        import threading
+
+        import torch
+
+        self.Q, self.X, self.k, self.out, self.err = Q, X, k, None, None
+        self.stream = torch.cuda.Stream(device=X.device)
+        self.stream.wait_stream(torch.cuda.current_stream(X.device))
+        self.th = threading.Thread(target=self._run, daemon=True)
+        self.th.start()
+
+    def _run(self):
+        import torch
+
+        from leann_amd.exact import exact_topk_ip
+
+        try:
+            torch.cuda.set_device(self.X.device)
+            parts = []
+            with torch.cuda.stream(self.stream):
+                for b0 in range(0, self.Q.shape[0], 256):
+                    parts.append(exact_topk_ip(self.Q[b0 : b0 + 256], self.X, self.k)[1])
+                    self.stream.synchronize()
+                self.out = torch.cat(parts).cpu().numpy()
+        except Exception as ex:  # noqa: BLE001 - re-raised by result()
+            self.err = ex
+
+    def result(self):
+        self.th.join()
+        if self.err is not None:
+            raise self.err
+        return self.out
+
+
+def _load_encoder(model):
+    """BertEncoder.load(model, allow_random=True).  Where no local checkpoint can exist -- `model` names no path and the Hugging Face cache
+    holds no config.json for it -- load() imports transformers only to find that out (seconds of a plain run's set-up) and returns the
+    seeded random weights of the preset architecture: those are made here directly (the same bits)."""
+    from leann_amd.encoder import BertEncoder, config_for
+
+    try:
+        from huggingface_hub import try_to_load_from_cache
+
+        no_checkpoint = not Path(model).exists() and not isinstance(try_to_load_from_cache(model, "config.json"), str)
+    except Exception:  # noqa: BLE001 - not a hub id, no hub client: let load() decide
+        no_checkpoint = False
+    if not no_checkpoint:
+        return BertEncoder.load(model, allow_random=True)
+    log(f"embedding model {model!r}: no local checkpoint; using SEEDED RANDOM weights of the preset architecture")
+    return BertEncoder.random_init(config_for(model), 0)
+
+
+def dump_outputs(out_dir, out):
+    """What one search call returned -- distances f32 and labels (int32 ids, exact in f64) -- as out_dir/distances.npy and out_dir/labels.npy."""
+    d, l = out
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "distances.npy"), d.float().cpu().numpy())
+    np.save(os.path.join(out_dir, "labels.npy"), l.cpu().numpy().astype(np.float64))
+    log(f"outputs of the last timed step written to {out_dir}: distances {tuple(d.shape)}, labels {tuple(l.shape)}")
 
 
 def main():
@@ -74,7 +206,7 @@ def main():
     ap.add_argument("--no-parity-check", action="store_true", help="skip the untimed GPU-vs-oracle parity check on the benchmark's own index")
     ap.add_argument("--no-latency-rows", action="store_true", help="skip the small-batch (B = 1, 16, 64, 256) latency rows and value_by_batch")
     ap.add_argument("--no-provider-ab", action="store_true", help="skip the extra full-size step over the Python form of the provider")
-    ap.add_argument("--extra-batches", default="", help="comma-separated batch sizes: one extra search call each on fresh queries after the timed steps (library defaults), "
+    ap.add_argument("--extra-batches", default="", help="with --full: comma-separated batch sizes, one extra search call each on fresh queries after the timed steps (library defaults), "
                     "reported as extra_batch_rows -- e.g. 128 = the per-rank batch of C5 (query batch 1024) on 8 GPUs")
     ap.add_argument("--fixed-len", type=int, default=0, help="SURVEY 8(d) variant: every chunk exactly this many tokens (256: 6.06 GFLOP per chunk), instead of len ~ N(180, 50)")
     ap.add_argument("--box-probe-only", action="store_true",
@@ -85,6 +217,12 @@ def main():
     ap.add_argument("--dry-run-emulated", default=None, metavar="LIB",
                     help="TEST ONLY (tests/test_bench_dry_run.py): run this script's control flow -- incl. every world > 1 branch, over gloo -- on the CPU against "
                          "the thread-per-lane build of the library (tests/hip_emul), with a tiny model and corpus; the line says data = dry-run and measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything that is not the headline figure: ef sweep, stored-embedding roofline, box probe, memo-off steps, profiled step, "
+                         "extra steps, latency rows, value by batch, parity check, CPU baseline (off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (distances f32, labels as f64) to DIR/<name>.npy")
     args = ap.parse_args()
     if args.box_probe_only:
         return _box_probe_only()
@@ -148,18 +286,33 @@ def _main(args, ap):
         if args.batch == defaults["batch"]:
             args.batch = max(1, 1024 // int(os.environ.get("WORLD_SIZE", "1")))
 
+    from leann_amd.synth import CorpusSpec, SyntheticCorpus
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    K, W, B = args.steps, args.warmup, args.batch
+    full = bool(args.full)
+    EXTRA_ROWS = 8192 if not dry else 32  # small-batch latency rows (library-side provider, then the Python provider) + parity-check queries (fresh, after every step's block)
+    n_q = B * (K + W + 5) + EXTRA_ROWS  # +5: the profiled step and the extra steps (smallest ef reaching recall 0.9; hub cache; two-level search; one spare)
+    t_setup = time.time()
+    spec = (CorpusSpec(n_chunks=args.chunks, seed=1234, vocab_size=2000, n_topics=8, len_mean=10.0, len_std=3.0, len_min=4, len_max=20) if dry else
+            CorpusSpec(n_chunks=args.chunks, seed=1234) if not args.fixed_len else
+            CorpusSpec(n_chunks=args.chunks, seed=1234, len_mean=float(args.fixed_len), len_std=0.0, len_min=args.fixed_len, len_max=args.fixed_len))
+    corpus = SyntheticCorpus(spec)
+    # the host-side corpus (and the queries) are generated by worker processes forked before torch is imported, while this process
+    # imports torch and loads the library; the same blocks as SyntheticCorpus.chunks() with the same per-block seeds (identical bits)
+    gpu_corpus = args.chunks >= 2_000_000 and not dry
+    host_gen = _HostCorpus(corpus, n_q * world, gpu_corpus)
+
     import torch
     import torch.distributed as dist
 
     from leann_amd import _lib
-    from leann_amd.encoder import BertEncoder, config_for
+    from leann_amd.encoder import config_for
     from leann_amd.gpu_graph_build import build_graph_gpu
     from leann_amd.index import Mi355xIndex
     from leann_amd.recompute import RecomputeProvider
-    from leann_amd.synth import CorpusSpec, SyntheticCorpus
     from leann_amd.token_store import TokenStore
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     _lib.require_gpu()
@@ -172,7 +325,6 @@ def _main(args, ap):
         else:
             dist.init_process_group("nccl", device_id=dev)
 
-    K, W, B = args.steps, args.warmup, args.batch
     # HIP-event pairs around every launch of the dominant kernel for the WHOLE process, recorded by the library itself (csrc/lm_timing.cpp)
     # and read out phase by phase: the roofline line uses the launches of the timed region; the all-launch average is what a rocprofv3
     # --kernel-trace --stats table of this same command reports for the kernel.
@@ -180,6 +332,7 @@ def _main(args, ap):
     KT_NAMES = {_lib.KT_LAYER_TAIL: "lm::k_layer_tail_h384", _lib.KT_GEMM_WS: "lm::k_gemm_ws_h384", _lib.KT_ATTN: "lm::k_attn_varlen", _lib.KT_GEMM_F16: "lm::k_gemm_f16",
                 _lib.KT_QKV: "lm::k_qkv_h384", _lib.KT_QKV_ATTN: "lm::k_qkv_attn_h384"}
     _lib.kernel_timing_enable(1 << kt_dominant)
+    log(f"torch and the library loaded ({time.time() - t_setup:.1f}s)")
     kt_phase = {}  # phase -> {kernel: {"launches", "ms", "work"}}
 
     def kt_close(phase):  # fold everything recorded since the previous call into `phase`
@@ -191,25 +344,17 @@ def _main(args, ap):
                 a_[f_] += v_[f_]
         return acc
 
-    EXTRA_ROWS = 8192 if not dry else 32  # small-batch latency rows (library-side provider, then the Python provider) + parity-check queries (fresh, after every step's block)
-    n_q = B * (K + W + 5) + EXTRA_ROWS  # +5: the profiled step and the extra steps (smallest ef reaching recall 0.9; hub cache; two-level search; one spare)
-    t_setup = time.time()
+    # ---- encoder (while the host corpus is being generated) -------------------------------------
+    cfg = config_for(args.model)
+    enc = _load_encoder(args.model).to(dev, dtype=torch.float16).eval()
+    D = cfg.hidden
 
     # ---- corpus -> HBM token store ------------------------------------------------------------
-    spec = (CorpusSpec(n_chunks=args.chunks, seed=1234, vocab_size=2000, n_topics=8, len_mean=10.0, len_std=3.0, len_min=4, len_max=20) if dry else
-            CorpusSpec(n_chunks=args.chunks, seed=1234) if not args.fixed_len else
-            CorpusSpec(n_chunks=args.chunks, seed=1234, len_mean=float(args.fixed_len), len_std=0.0, len_min=args.fixed_len, len_max=args.fixed_len))
-    corpus = SyntheticCorpus(spec)
     # 2M chunks and more (C5: 10M): the same generative model evaluated on the GPU (3 s instead of 195 s per 10M chunks; deterministic, but
     # not the numpy path's bits -- the 1M-chunk default keeps the numpy corpus every round so far has been measured on)
-    tok, off = corpus.chunks_torch(dev) if (args.chunks >= 2_000_000 and not dry) else corpus.chunks()
+    tok, off = corpus.chunks_torch(dev) if gpu_corpus else host_gen.chunks()
     tokens = TokenStore(tok, off, device=lib_dev)
     log(f"corpus: {args.chunks} chunks, {int(off[-1])} tokens ({time.time() - t_setup:.1f}s)")
-
-    # ---- encoder ------------------------------------------------------------------------------
-    cfg = config_for(args.model)
-    enc = BertEncoder.load(args.model, allow_random=True).to(dev, dtype=torch.float16).eval()
-    D = cfg.hidden
     provider = RecomputeProvider(enc, tokens, (D + 63) // 64 * 64, dev)
 
     # ---- embeddings of every chunk + graph (index build time only): built ONCE, on rank 0, then replicated over RCCL ----
@@ -224,7 +369,18 @@ def _main(args, ap):
             X[b0 : b0 + ids.shape[0]] = provider.embed_ids(ids)
         torch.cuda.synchronize()
         t_embed = time.time() - t0
-        log(f"embedded corpus in {t_embed:.1f}s ({args.chunks / t_embed:.0f} chunks/s)")
+        log(f"embedded corpus in {t_embed:.1f}s ({args.chunks / t_embed:.0f} chunks/s; {time.time() - t_setup:.1f}s)")
+
+    # ---- queries + exact ground truth (blocked: no GEMM call with more than 2^28 output elements, leann_amd/exact.py says why; a plain run
+    #      needs the timed rows only).  With one rank the ground truth is computed while the graph is built ----------------------------
+    qt, qo, _ = host_gen.queries()
+    qstore = TokenStore(qt, qo, device=lib_dev)
+    Q_all = RecomputeProvider(enc, qstore, provider.dp, dev).embed_ids(torch.arange(n_q * world, dtype=torch.int32, device=dev))
+    Q = Q_all[rank * n_q : (rank + 1) * n_q].contiguous()
+    n_gt = n_q if full else (W + K) * B
+    gt_bg = _GroundTruth(Q[:n_gt], X, 10) if (world == 1 and not dry) else None
+
+    if rank == 0:
         t0 = time.time()
         g = build_graph_gpu(X, "mips", M=args.M, ef_construction=args.efc, verbose=bool(os.environ.get("BENCH_VERBOSE")))
         t_graph = time.time() - t0
@@ -237,18 +393,16 @@ def _main(args, ap):
         torch.cuda.synchronize()
         log(f"index replicated to {world} ranks in {time.time() - t0:.1f}s")
     deg0 = g.level0_degrees()
-    log(f"graph built in {t_graph:.1f}s: max_level={g.max_level} mean level-0 degree={deg0.mean():.1f} edges={g.neighbors.shape[0]}")
+    log(f"graph built in {t_graph:.1f}s ({time.time() - t_setup:.1f}s): max_level={g.max_level} mean level-0 degree={deg0.mean():.1f} edges={g.neighbors.shape[0]}")
     idx = Mi355xIndex.from_csr(g, device=lib_dev)
     idx.set_stream(torch.cuda.current_stream().cuda_stream)
+    if gt_bg is not None:
+        gt_np = gt_bg.result()
+    else:
+        from leann_amd.exact import exact_topk_ip
 
-    # ---- queries + exact ground truth ------------------------------------------------------------
-    qt, qo, _ = corpus.queries(n_q * world, seed=4321)
-    qstore = TokenStore(qt, qo, device=lib_dev)
-    Q_all = RecomputeProvider(enc, qstore, provider.dp, dev).embed_ids(torch.arange(n_q * world, dtype=torch.int32, device=dev))
-    Q = Q_all[rank * n_q : (rank + 1) * n_q].contiguous()
-    from leann_amd.exact import exact_topk_ip
-
-    gt_np = exact_topk_ip(Q, X, 10)[1].cpu().numpy()  # blocked: no GEMM call with more than 2^28 output elements (leann_amd/exact.py says why)
+        gt_np = exact_topk_ip(Q[:n_gt], X, 10)[1].cpu().numpy()
+    log(f"ground truth of {gt_np.shape[0]} queries ({time.time() - t_setup:.1f}s)")
 
     def recall(labels_np, rows):
         hit = 0
@@ -260,18 +414,19 @@ def _main(args, ap):
     idx.attach_table(X)
     sweep = {}
     nsel = min(n_q, 512)
-    for ef in (16, 32, 64, 128, 256):
+    for ef in (16, 32, 64, 128, 256) if (full or not args.ef) else ():
         _, l = idx.search_device(Q[:nsel], 10, idx.make_params(ef=ef, beam=args.beam, recompute=False))
         st = idx.stats()
         sweep[ef] = {"recall": recall(l.cpu().numpy(), range(nsel)), "ndis_per_query": st["ndis"] / nsel}
-    log("ef sweep (stored-embedding mode):", json.dumps(sweep))
+    if sweep:
+        log("ef sweep (stored-embedding mode):", json.dumps(sweep))
     ef_min = next((e for e in sorted(sweep) if sweep[e]["recall"] >= 0.9), 256)
     ef = args.ef or ef_min
 
     # optional: HBM-gather roofline of the fused kernel in stored-embedding mode, big batch
     table_roof = None
     extras_errors = {}
-    if args.table_roofline and world == 1:
+    if full and args.table_roofline and world == 1:
         try:
             idx.set_profiling(True)
             # 32768 DISTINCT queries of their own (held-out chunks, another seed than the timed queries'): no row gather of this measurement is a
@@ -352,20 +507,24 @@ def _main(args, ap):
     out_labels = []
     # what box is this?  (reference launches of the dominant kernel + a copy rate on the idle chip, before anything is timed)
     probe = None
-    if cfg.hidden == 384 and not dry and not args.no_box_probe:
+    if full and cfg.hidden == 384 and not dry and not args.no_box_probe:
         probe = box_probe(enc, dev, local_rank, counter_pass=(rank == 0 and world == 1))  # (the counter pass runs a child process on device 0: single-GPU runs only)
         log("box probe:", json.dumps(probe)[:600])
     kt_close("setup")
+    t_warm = time.perf_counter()
     for w in range(W):
         ps.search(batches[w], 10)
     agg = {"ndis": 0, "nunique": 0, "nrounds": 0, "update_launches": 0}
     provider.chunks = 0
     barrier()
+    log(f"warm-up: {W} steps in {time.perf_counter() - t_warm:.1f}s")
     kt_close("warmup")
     sampler = BoxSampler(local_rank, period_s=0.25).start() if (probe is not None and rank == 0) else None  # a thread reading sysfs four times a second (rocm-smi every 5 s where sysfs has no clocks)
+    last_out = None
     t0 = time.perf_counter()
     for s in range(K):
-        _, l = ps.search(batches[W + s], 10)
+        last_out = ps.search(batches[W + s], 10)
+        l = last_out[1]
         out_labels.append(l[rank * B : (rank + 1) * B])
         st = idx.stats()
         for k_ in agg:
@@ -375,10 +534,13 @@ def _main(args, ap):
     if sampler is not None:
         probe["clocks_during_the_timed_steps"] = sampler.stop()
     ktimes = kt_close("timed")  # (reading waits for the last pairs: after the clock has stopped)
+    if args.dump_outputs and rank == 0 and last_out is not None:  # what the caller of the timed path received in the last timed step
+        dump_outputs(args.dump_outputs, last_out)
+    del last_out
     # ---- the same steps WITHOUT the per-call memo (dedup per lock-step round only: rounds 1 / 2's `value`), on the same queries:
     #      K2 = min(K, 3) steps (one, when a step takes more than 20 s) after one warm-up step, same bracketing; labels must be identical to
     #      the memo steps' ----------
-    K2 = min(K, 3) if elapsed / max(K, 1) < 20.0 else min(K, 1)  # (a 58-second step -- C5 at 10M chunks -- gets one memo-off step, not three)
+    K2 = 0 if not full else min(K, 3) if elapsed / max(K, 1) < 20.0 else min(K, 1)  # (a 58-second step -- C5 at 10M chunks -- gets one memo-off step, not three)
     prm_nomemo = idx.make_params(ef=ef, beam=args.beam, recompute=True, max_batch=B, recompute_memo=False)
     ps_nm = PartitionedSearch(lambda qq, k: idx.search_device(qq, k, prm_nomemo))
     if K2:
@@ -408,22 +570,24 @@ def _main(args, ap):
         elapsed, elapsed_nm, same_labels = float(t[0].item()), float(t[1].item()), float(t[2].item()) == 0.0
     # ---- one more step of the same workload WITH profiling (HIP event pairs + device span stamps per launch): the
     #      source of the roofline figures; not part of `value` ----------------------------------------------------
-    idx.set_profiling(True)
-    _lib.kernel_timing_enable((1 << _lib.KT_COUNT) - 1)  # every instrumented encoder kernel, this one step only
-    lo = (W + K) * B
-    torch.cuda.synchronize()
-    t1p = time.perf_counter()
-    idx.search_device(Q[lo : lo + B], 10, prm)
-    torch.cuda.synchronize()
-    prof_step_s = time.perf_counter() - t1p
-    prof = idx.stats()
-    kprof = kt_close("profiled")
-    _lib.kernel_timing_enable(1 << kt_dominant)
-    idx.set_profiling(False)
+    prof = kprof = None
+    if full:
+        idx.set_profiling(True)
+        _lib.kernel_timing_enable((1 << _lib.KT_COUNT) - 1)  # every instrumented encoder kernel, this one step only
+        lo = (W + K) * B
+        torch.cuda.synchronize()
+        t1p = time.perf_counter()
+        idx.search_device(Q[lo : lo + B], 10, prm)
+        torch.cuda.synchronize()
+        prof_step_s = time.perf_counter() - t1p
+        prof = idx.stats()
+        kprof = kt_close("profiled")
+        _lib.kernel_timing_enable(1 << kt_dominant)
+        idx.set_profiling(False)
     # ---- extras (NOT `value`; single-GPU runs only -- they contain no collectives and may never cost the headline
     #      line): one extra step each, on fresh queries ----------------------------------------------------------
     min_ef = with_hub = two_level = None
-    do_extras = world == 1 and not args.no_min_ef_step
+    do_extras = full and world == 1 and not args.no_min_ef_step
 
     def extra_step(params, slot):
         lo_ = (W + K + 1 + slot) * B
@@ -479,7 +643,7 @@ def _main(args, ap):
     # The timed steps above already ran over the product default: the LIBRARY-side provider (csrc/lm_recompute.hip -- no interpreter
     # in the search loop, one host synchronisation per round).  The Python form of the provider is the A/B here.
     latency_python_provider = provider_ab = latency_speculate = None
-    if world == 1 and not args.no_latency_rows:
+    if full and world == 1 and not args.no_latency_rows:
         try:
             latency_rows, next_row = small_batch_latency(
                 idx, Q, lambda b: idx.make_params(ef=ef, beam=args.beam, recompute=True, max_batch=b), recall, next_row)
@@ -507,12 +671,12 @@ def _main(args, ap):
         except Exception as ex:  # noqa: BLE001
             extras_errors["small_batch_latency"] = repr(ex)[:300]
     frontier = None
-    if world == 1 and not args.no_latency_rows:
+    if full and world == 1 and not args.no_latency_rows:
         try:
             frontier = latency_frontier(idx, Q, recall, next_row)
         except Exception as ex:  # noqa: BLE001
             extras_errors["small_batch_latency_frontier"] = repr(ex)[:300]
-    if world == 1 and idx.native_provider and K and not args.no_provider_ab:  # one full-size step over the PYTHON provider, on a timed step's own queries: same labels
+    if full and world == 1 and idx.native_provider and K and not args.no_provider_ab:  # one full-size step over the PYTHON provider, on a timed step's own queries: same labels
         os.environ["LEANN_MI355X_NATIVE_PROVIDER"] = "0"
         try:
             idx.set_provider(provider)
@@ -534,7 +698,7 @@ def _main(args, ap):
     #      the memo's gain is a property of B / N (it is what cross-query dedup buys when a call re-embeds a large part of the corpus) ----
     value_by_batch = None
     chunks_per_s = (args.chunks / t_embed) if t_embed > 0 else None  # encoder throughput of this run (corpus embedding at index-build time)
-    if world == 1 and not args.no_latency_rows:
+    if full and world == 1 and not args.no_latency_rows:
         try:
             value_by_batch = []
             for b in (64, 256, 8192):
@@ -560,7 +724,7 @@ def _main(args, ap):
         except Exception as ex:  # noqa: BLE001
             extras_errors["value_by_batch"] = repr(ex)[:300]
     extra_batch_rows = None
-    if world == 1 and args.extra_batches:
+    if full and world == 1 and args.extra_batches:
         try:
             extra_batch_rows = []
             for b in (int(v) for v in args.extra_batches.split(",") if v):
@@ -581,7 +745,7 @@ def _main(args, ap):
                                          "note": "one call after one warm-up call of the same batch size on other queries"})
         except Exception as ex:  # noqa: BLE001
             extras_errors["extra_batch_rows"] = repr(ex)[:300]
-    if world == 1 and not args.no_parity_check:
+    if full and world == 1 and not args.no_parity_check:
         try:
             t1 = time.time()
             parity = parity_check(idx, g, X, Q[min(next_row, n_q - 272):], provider, ef, args.beam, D)
@@ -596,45 +760,47 @@ def _main(args, ap):
         rec = float(t.item()) / world
     qps = world * K * B / elapsed if elapsed > 0 else 0.0
 
-    # ---- roofline of the hand-written distance/beam-update kernel (HIP events, timed region) -------
-    bytes_eval = D * 4 + 4  # D*s_e + 4 (id); the distance never goes back to HBM (fused)
-    # Per-launch duration = the kernel's execution span measured ON the device (per-workgroup wall-clock stamps,
-    # max end - min start): the same quantity rocprofv3 --kernel-trace --stats reports.  The HIP-event pair around
-    # each launch (which also contains dispatch latency) is reported next to it.
-    ev_over = idx.event_overhead_us()
-    raw_us = 1e3 * prof["update_ms"] / max(prof["update_launches"], 1)
-    net_us = 1e3 * prof["update_span_ms"] / max(prof["update_span_launches"], 1)
-    upd_s = prof["update_span_ms"] * 1e-3
-    achieved = prof["ndis"] * bytes_eval / upd_s / 1e9 if upd_s > 0 else 0.0
-    traffic = None
-    traffic_src = None
-    try:  # HBM bytes per launch from the separate PMC pass (profiles/r1_pmc_k_update.json), scaled to this run's launch size
-        pmc_file = next(f for f in ("r4_pmc_k_update.json", "r1_pmc_k_update.json") if (ROOT / "profiles" / f).exists())
-        pmc = json.loads((ROOT / "profiles" / pmc_file).read_text())
-        per_eval = pmc.get("hbm_bytes_per_eval") or pmc.get("hbm_bytes_per_eval_corrected_x1.36") or pmc.get("hbm_bytes_per_eval_corrected_x1.08")
-        if per_eval:
-            traffic = round(per_eval * prof["ndis"] / max(prof["update_launches"], 1))
-            traffic_src = (f"rocprofv3 --pmc FETCH_SIZE pass on scripts/kernel_bench.py --provider (profiles/{pmc_file}), calibrated on a known byte count measured "
-                           "in the same pass, scaled by evals/launch")
-        else:
-            traffic_src = f"profiles/{pmc_file} carries no hbm_bytes_per_eval key: traffic not reported"
-    except Exception as ex:  # noqa: BLE001
-        traffic_src = "no PMC file of the distance kernel could be read: " + repr(ex)[:120]
-    roofline_dist = {"bound": "hbm", "kernel": "lm::k_update<6,false,false,1,256> (fused gather + distance + beam update, recompute mode)", "achieved": round(achieved, 2),
-                "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": round(bytes_eval * prof["ndis"] / max(prof["update_launches"], 1)),
-                "bytes_per_eval": bytes_eval, "evals_per_launch": round(prof["ndis"] / max(prof["update_launches"], 1), 1),
-                "us_per_launch": round(net_us, 2), "us_per_launch_event_pair": round(raw_us, 2), "empty_kernel_event_pair_us": round(ev_over, 2),
-                "timing": "device wall-clock span per launch (HIP events alongside), from one profiled step after the timed ones",
-                "profiled_step_ms": round(1e3 * prof_step_s, 1)}
-    # encoder (MFMA bound): flops of the chunks actually recomputed / HIP-event time of the provider
-    lens = np.diff(off.astype(np.int64))
-    mean_flops = float(np.mean([cfg.flops_per_chunk(int(t)) for t in np.random.default_rng(0).choice(lens, 4096)]))
-    enc_tf = prof["nunique"] * mean_flops / (prof["provider_ms"] * 1e-3) / 1e12 if prof["provider_ms"] > 0 else 0.0
-    roofline_encoder = {"bound": "mfma", "achieved": round(enc_tf, 2), "peak": 2500.0, "unit": "TFLOP/s",
-                        "frac": round(enc_tf / 2500.0, 5), "chunks_per_query": round(agg["nunique"] / max(K * B, 1), 1),
-                        "mean_gflop_per_chunk": round(mean_flops / 1e9, 3), "provider_ms_share": round(prof["provider_ms"] / (prof_step_s * 1e3), 4),
-                        "whole_step_TFLOPs": round(agg["nunique"] * mean_flops / max(elapsed, 1e-9) / 1e12, 2)}
+    roofline_dist = roofline_encoder = None
+    if full:  # both come from the profiled step
+        # ---- roofline of the hand-written distance/beam-update kernel (HIP events, timed region) -------
+        bytes_eval = D * 4 + 4  # D*s_e + 4 (id); the distance never goes back to HBM (fused)
+        # Per-launch duration = the kernel's execution span measured ON the device (per-workgroup wall-clock stamps,
+        # max end - min start): the same quantity rocprofv3 --kernel-trace --stats reports.  The HIP-event pair around
+        # each launch (which also contains dispatch latency) is reported next to it.
+        ev_over = idx.event_overhead_us()
+        raw_us = 1e3 * prof["update_ms"] / max(prof["update_launches"], 1)
+        net_us = 1e3 * prof["update_span_ms"] / max(prof["update_span_launches"], 1)
+        upd_s = prof["update_span_ms"] * 1e-3
+        achieved = prof["ndis"] * bytes_eval / upd_s / 1e9 if upd_s > 0 else 0.0
+        traffic = None
+        traffic_src = None
+        try:  # HBM bytes per launch from the separate PMC pass (profiles/r1_pmc_k_update.json), scaled to this run's launch size
+            pmc_file = next(f for f in ("r4_pmc_k_update.json", "r1_pmc_k_update.json") if (ROOT / "profiles" / f).exists())
+            pmc = json.loads((ROOT / "profiles" / pmc_file).read_text())
+            per_eval = pmc.get("hbm_bytes_per_eval") or pmc.get("hbm_bytes_per_eval_corrected_x1.36") or pmc.get("hbm_bytes_per_eval_corrected_x1.08")
+            if per_eval:
+                traffic = round(per_eval * prof["ndis"] / max(prof["update_launches"], 1))
+                traffic_src = (f"rocprofv3 --pmc FETCH_SIZE pass on scripts/kernel_bench.py --provider (profiles/{pmc_file}), calibrated on a known byte count measured "
+                               "in the same pass, scaled by evals/launch")
+            else:
+                traffic_src = f"profiles/{pmc_file} carries no hbm_bytes_per_eval key: traffic not reported"
+        except Exception as ex:  # noqa: BLE001
+            traffic_src = "no PMC file of the distance kernel could be read: " + repr(ex)[:120]
+        roofline_dist = {"bound": "hbm", "kernel": "lm::k_update<6,false,false,1,256> (fused gather + distance + beam update, recompute mode)", "achieved": round(achieved, 2),
+                    "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 5), "traffic": traffic, "traffic_source": traffic_src,
+                    "algorithmic_bytes_per_launch": round(bytes_eval * prof["ndis"] / max(prof["update_launches"], 1)),
+                    "bytes_per_eval": bytes_eval, "evals_per_launch": round(prof["ndis"] / max(prof["update_launches"], 1), 1),
+                    "us_per_launch": round(net_us, 2), "us_per_launch_event_pair": round(raw_us, 2), "empty_kernel_event_pair_us": round(ev_over, 2),
+                    "timing": "device wall-clock span per launch (HIP events alongside), from one profiled step after the timed ones",
+                    "profiled_step_ms": round(1e3 * prof_step_s, 1)}
+        # encoder (MFMA bound): flops of the chunks actually recomputed / HIP-event time of the provider
+        lens = np.diff(off.astype(np.int64))
+        mean_flops = float(np.mean([cfg.flops_per_chunk(int(t)) for t in np.random.default_rng(0).choice(lens, 4096)]))
+        enc_tf = prof["nunique"] * mean_flops / (prof["provider_ms"] * 1e-3) / 1e12 if prof["provider_ms"] > 0 else 0.0
+        roofline_encoder = {"bound": "mfma", "achieved": round(enc_tf, 2), "peak": 2500.0, "unit": "TFLOP/s",
+                            "frac": round(enc_tf / 2500.0, 5), "chunks_per_query": round(agg["nunique"] / max(K * B, 1), 1),
+                            "mean_gflop_per_chunk": round(mean_flops / 1e9, 3), "provider_ms_share": round(prof["provider_ms"] / (prof_step_s * 1e3), 4),
+                            "whole_step_TFLOPs": round(agg["nunique"] * mean_flops / max(elapsed, 1e-9) / 1e12, 2)}
 
     # `roofline` = the DOMINANT kernel of the timed region: the fused second half of an encoder layer (attention output projection,
     # LayerNorm, feed-forward block, LayerNorm: 70 % of the encoder's flops, the largest share of the step's time), MFMA bound;
@@ -724,9 +890,13 @@ def _main(args, ap):
                       "rounds_per_step": round(agg["nrounds"] / max(K, 1), 1)},
         "setup_s": {"total": round(setup_s, 1), "embed_corpus": round(t_embed, 1), "build_graph": round(t_graph, 1)},
     }
+    if not full:  # a plain run measured none of these
+        for k_ in ("without_call_memo", "roofline_distance_kernel", "roofline_encoder") + (() if sweep else ("ef_sweep",)):
+            result.pop(k_)
     # the driver's record keeps `config` and `roofline` whole but truncates the tail of the line: the kernel-tracking figure (no per-call memo) goes there too
-    result["config"]["without_call_memo_queries_per_s"] = result["without_call_memo"]["value"]
-    if isinstance(result["roofline"], dict):
+    if full:
+        result["config"]["without_call_memo_queries_per_s"] = result["without_call_memo"]["value"]
+    if isinstance(result["roofline"], dict) and full:
         result["roofline"]["value_without_call_memo_queries_per_s"] = result["without_call_memo"]["value"]
         result["roofline"]["whole_encoder_TFLOPs"] = roofline_encoder["achieved"]
         if probe is not None:
@@ -783,10 +953,10 @@ def _main(args, ap):
     if extras_errors:
         result["extras_errors"] = extras_errors
 
-    if rank == 0:  # the line so far, on stderr: a run cut short inside the CPU baseline still leaves its GPU numbers in the log
+    if full and rank == 0:  # the line so far, on stderr: a run cut short inside the CPU baseline still leaves its GPU numbers in the log
         log("preliminary (before the CPU baseline): " + json.dumps({k: result[k] for k in ("value", "ms_per_step", "recall_at_10", "roofline", "roofline_encoder")}))
     # ---- CPU baseline (rank 0, N=1 only): the oracle + fp32 CPU encoder on a bounded sample ---------
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(args, g, Q, tok, off, cfg, ef, args.beam, X)
         except Exception as ex:  # noqa: BLE001 - report, never lose the line

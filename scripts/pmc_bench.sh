@@ -3,7 +3,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/pmc_bench; rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT" -o pmc -- python bench.py "$@" > "$OUT/run.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT" -o pmc -- python bench.py --full "$@" > "$OUT/run.log" 2>&1
 tail -1 "$OUT/run.log" | cut -c1-400
 python - "$OUT" <<'PY'
 import csv, glob, sys, collections, os

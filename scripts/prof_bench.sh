@@ -6,7 +6,7 @@ TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o "$TAG" -- python bench.py "$@" > "$OUT/bench.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o "$TAG" -- python bench.py --full "$@" > "$OUT/bench.log" 2>&1
 tail -3 "$OUT/bench.log"
 find "$OUT" -name "*kernel_trace.csv" -size +8M -delete
 find "$OUT" -name "*.db" -delete

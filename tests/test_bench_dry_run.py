@@ -11,6 +11,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -47,7 +48,7 @@ def _last_json(stdout):
 
 def test_bench_py_control_flow_on_two_ranks(emul_lib, world=2):
     common = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--chunks", "200", "--batch", "2", "--M", "8", "--efc", "24", "--ef", "16",
-              "--no-cpu-baseline", "--no-table-roofline", "--no-parity-check", "--no-latency-rows", "--no-min-ef-step", "--dry-run-emulated", str(emul_lib)]
+              "--full", "--no-cpu-baseline", "--no-table-roofline", "--no-parity-check", "--no-latency-rows", "--no-min-ef-step", "--dry-run-emulated", str(emul_lib)]
     if world == 1:
         cmd = [sys.executable] + common
     else:
@@ -64,6 +65,43 @@ def test_bench_py_control_flow_on_two_ranks(emul_lib, world=2):
     assert nm["labels_identical_to_the_memo_steps"] is True and nm["value"] > 0  # all_reduce'd over the ranks
     assert line["roofline"]["bound"] in ("mfma", "hbm")
     assert r.stdout.count("\n{") + r.stdout.startswith("{") == 1  # ONE line, rank 0 only
+
+
+def test_bench_py_plain_run_and_dump_outputs(emul_lib, tmp_path):
+    """A plain run (no --full) times --steps steps and measures nothing else; --dump-outputs writes what the last timed step returned, and
+    two runs with the same arguments write the same arrays."""
+    common = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--chunks", "200", "--batch", "2", "--M", "8", "--efc", "24",
+              "--ef", "16", "--dry-run-emulated", str(emul_lib), "--dump-outputs"]
+    dumps = []
+    for i in range(2):
+        r = _run(common + [str(tmp_path / f"run{i}")], 900)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+        line = _last_json(r.stdout)
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "queries/s" and line["higher_is_better"] is True and line["dtype"] == "fp16" and "recall_at_10" in line
+        for k in ("without_call_memo", "roofline_distance_kernel", "roofline_encoder", "ef_sweep", "cpu_baseline", "parity_check", "small_batch_latency"):
+            assert k not in line, k
+        d, l = np.load(tmp_path / f"run{i}" / "distances.npy"), np.load(tmp_path / f"run{i}" / "labels.npy")
+        assert d.dtype == np.float32 and l.dtype == np.float64 and d.shape == l.shape == (2, 10)
+        assert np.all(l >= -1) and np.all(l < 200) and np.array_equal(l, np.rint(l))
+        dumps.append((d, l))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_bench_host_corpus_is_the_serial_corpus():
+    """bench.py generates the numpy corpus and the queries in worker processes: the same bits as SyntheticCorpus.chunks() / .queries()."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from leann_amd.synth import CorpusSpec, SyntheticCorpus
+
+    c = SyntheticCorpus(CorpusSpec(n_chunks=3 * bench.CORPUS_BLOCK + 17, seed=1234, len_mean=12.0, len_std=4.0, len_min=4, len_max=24))
+    h = bench._HostCorpus(c, 300)
+    tok, off = h.chunks()
+    qt, qo, qd = h.queries()
+    tok2, off2 = c.chunks()
+    qt2, qo2, qd2 = c.queries(300, seed=4321)
+    for a, b in ((tok, tok2), (off, off2), (qt, qt2), (qo, qo2), (qd, qd2)):
+        assert a.dtype == b.dtype and np.array_equal(a, b)
 
 
 def test_bench_c4_sharded_control_flow_on_two_ranks(emul_lib):
