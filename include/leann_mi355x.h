@@ -244,6 +244,28 @@ int lm_dist_gather(const void *d_table, int32_t dtype, int32_t d_padded, int32_t
  * in: S x B x k, out: B x k, ordered by (internal distance, id). */
 int lm_topk_merge(const int64_t *d_in_ids, const float *d_in_dist, int32_t S, int32_t B, int32_t k,
                   int32_t metric, int64_t *d_out_ids, float *d_out_dist, void *stream);
+/* Index build time: the select-neighbours heuristic of HNSW construction (Malkov & Yashunin Alg. 4 = faiss shrink_neighbor_list), which
+ * faiss runs inside index.add under index.hnsw.efConstruction (leann_backend_hnsw/hnsw_backend.py:66-94) and the LEANN paper's Alg. 3
+ * (high-degree-preserving pruning) calls again; n rows at once, every pairwise distance by the canonical reduction of
+ * oracle/lm_oracle.c:orc_dist.
+ *   d_table [ntable][d_padded]  fp32 or fp16 rows, zero padded (lm_dist_gather's layout);
+ *   d_cand  [n][K]              candidate row ids, best first; an id < 0 or >= ntable is an EMPTY slot: never kept, never dereferenced;
+ *   d_dist  [n][K]              the candidates' INTERNAL distances to their row's base node (squared L2, or -ip: smaller is closer),
+ *                               taken as given, not recomputed;
+ *   d_keep  [n][K]              out: 1 = kept, 0 = not.
+ * Strict pass: scan j = 0 .. K-1; skip empty slots; stop keeping once m are kept; keep j unless some already kept i has
+ * dist(cand[j], cand[i]) <= d_dist[j] (plain IEEE comparison: NaN never dominates).  Relaxed pass, only when alpha != 1 (DiskANN
+ * occlude_list): scan the candidates not yet kept, in order, while fewer than m are kept, with thr[j] in place of d_dist[j], tested
+ * against everything kept so far; a2 = alpha * alpha in fp32, thr = d / a2 (L2), thr = -(1.0f - (1.0f + d) / a2) (inner product of
+ * unit vectors).  fp32 throughout, no contraction.
+ * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width the search kernels do not cover, K < 1 or K > LM_SELECT_MAX_K,
+ * m < 1, alpha < 1 or not finite, n < 0.  n == 0: LM_OK.
+ * LM_SELECT_MAX_K: the kept set is a K-bit mask in registers.  The batched builder reaches K = k_cand + 1 + cap = 193 at M = 32
+ * (257 at M = 64) when it refines level 0, and 2 cap = 128 when it shrinks an overflowing list. */
+#define LM_SELECT_MAX_K 512
+int lm_select_neighbors(const void *d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric,
+                        const int32_t *d_cand, const float *d_dist, int64_t n, int32_t K, int32_t m, float alpha,
+                        uint8_t *d_keep, void *stream);
 
 /* ---- fused encoder elementwise ops ---------------------------------------------------------------
  * out = LayerNorm(x + residual) * gamma + beta over the last dim; fp16 in/out, fp32 arithmetic;

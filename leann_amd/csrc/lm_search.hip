@@ -11,6 +11,7 @@
 //   k_memo_append per-call embedding memo (recompute_memo)
 //   k_search_table persistent stored-embedding search: a query's whole traversal in one workgroup, one launch/batch
 //   lm_pq_impl.h  DiskANN-style path: k_pq_traverse (persistent PQ-ADC traversal), k_pq_rerank
+//   lm_select_impl.h  index build time: k_select_neighbors (HNSW select-neighbours heuristic, 16 lanes per row)
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
 #include <algorithm>
@@ -1054,4 +1055,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 }  // extern "C"
 
 #include "lm_pq_impl.h"
+#include "lm_select_impl.h"
 

@@ -153,11 +153,59 @@ def _select_heuristic_selection(xs: torch.Tensor, cand: torch.Tensor, sim: torch
     return keep
 
 
+def _padded_table(xs: torch.Tensor) -> torch.Tensor:
+    """xs as the table layout of the library (lm_dist_gather / lm_select_neighbors): fp32 or fp16 rows, zero padded to a multiple of 64,
+    contiguous.  A table that already has that layout is returned as it is (no copy): callers pad once and select many times."""
+    dt = xs.dtype if xs.dtype in (torch.float32, torch.float16) else torch.float32
+    d = xs.shape[1]
+    dp = (d + 63) // 64 * 64
+    if d == dp and xs.dtype == dt and xs.is_contiguous():
+        return xs
+    t = torch.zeros((xs.shape[0], dp), dtype=dt, device=xs.device)
+    t[:, :d] = xs
+    return t
+
+
+@torch.no_grad()
+def select_neighbors_kernel(xs: torch.Tensor, cand: torch.Tensor, sim: torch.Tensor, m: int, metric: int, alpha: float = 1.0):
+    """_select_heuristic's contract (cand [n, K], -1 = empty, sim [n, K] best first -> bool keep mask [n, K]) on the library's kernel
+    (lm_select_neighbors): the same scan, but every pairwise distance is the canonical fp32 reduction -- not an fp16 bmm -- so the mask is
+    pinned bit for bit by a CPU restatement (tests/select_ref).  ``xs``: the embeddings, fp32 or fp16; pass a table that is already
+    padded (_padded_table) when selecting repeatedly over the same rows."""
+    from . import _lib
+
+    n, K = cand.shape
+    keep = torch.zeros((n, K), dtype=torch.uint8, device=cand.device)
+    if n == 0 or K == 0:
+        return keep.bool()
+    tab = _padded_table(xs)
+    c32 = cand.to(torch.int32).contiguous()
+    dist = (-sim.to(torch.float32)).contiguous()  # similarity (ip, or -squared-l2) -> internal distance: an exact negation either way
+    stream = torch.cuda.current_stream(tab.device).cuda_stream if tab.is_cuda else None
+    rc = _lib.load().lm_select_neighbors(tab.data_ptr(), _lib.DTYPE_F16 if tab.dtype == torch.float16 else _lib.DTYPE_F32, tab.shape[0], tab.shape[1],
+                                         int(metric), c32.data_ptr(), dist.data_ptr(), n, K, int(m), float(alpha), keep.data_ptr(), stream)
+    _lib.check(rc, "lm_select_neighbors")
+    return keep.bool()
+
+
+SELECTORS = ("torch", "kernel")
+
+
+def _selector_fn(selector: str):
+    """selector -> f(xs, cand, sim, m, metric, alpha=...) -> keep mask.  "torch": the vectorised torch ops (the default); "kernel": the HIP kernel."""
+    if selector == "torch":
+        return _select_heuristic
+    if selector == "kernel":
+        return select_neighbors_kernel
+    raise ValueError(f"selector must be one of {SELECTORS}, not {selector!r}")
+
+
 class _LevelGraph:
     """Fixed-capacity adjacency of one level over the node subset ``sub`` (sorted global ids)."""
 
-    def __init__(self, sub: torch.Tensor, cap: int):
+    def __init__(self, sub: torch.Tensor, cap: int, selector: str = "torch"):
         n = sub.shape[0]
+        self._select = _selector_fn(selector)
         self.sub = sub
         self.cap = cap
         self.adj = torch.full((n, cap), -1, dtype=torch.int64, device=sub.device)
@@ -210,7 +258,7 @@ class _LevelGraph:
         new_sim = csim[:, :cap].clone()
         if bool(over.any()):
             oi = torch.nonzero(over).flatten()
-            keep = _select_heuristic(xs, cand[oi], csim[oi], cap, metric, alpha=self.alpha)
+            keep = self._select(xs, cand[oi], csim[oi], cap, metric, alpha=self.alpha)
             # compact kept entries to the front (stable)
             order = torch.argsort((~keep).int(), dim=1, stable=True)
             kc = torch.gather(cand[oi], 1, order)[:, :cap]
@@ -292,10 +340,13 @@ def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
 @torch.no_grad()
 def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_construction: int = 200, seed: int = 12345,
                     search_fn: Optional[SearchFn] = None, growth: float = 1.5, k_cand: int = 0,
-                    seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0) -> HnswCsr:
+                    seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch") -> HnswCsr:
     """x: [N, D] float tensor on the build device.  Returns the compact-CSR HNSW graph (host).  ``alpha`` > 1 relaxes the neighbour
     selection the way Vamana does (denser lists with longer edges: what a PQ-guided walk over a flat graph needs at 10M nodes -- DESIGN 8;
-    inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on."""
+    inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on.
+    ``selector``: "torch" (default) = neighbour selection by the vectorised torch ops, "kernel" = by lm_select_neighbors (canonical fp32
+    distances: a slightly different, oracle-pinned graph -- DESIGN.md)."""
+    select = _selector_fn(selector)
     metric = metric.lower()
     if metric not in ("mips", "cosine", "l2"):
         raise ValueError(f"Unsupported distance_metric '{metric}'.")
@@ -321,8 +372,9 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
         sub = torch.nonzero(lv_dev >= l).flatten()
         nl = sub.shape[0]
         xs = x[sub]
+        xsel = _padded_table(xs) if selector == "kernel" else xs  # what the selector reads: padded once per level
         cap = 2 * M if l == 0 else M
-        G = _LevelGraph(sub, cap)
+        G = _LevelGraph(sub, cap, selector)
         G.alpha = alpha
         inserted = torch.zeros(nl, dtype=torch.bool, device=dev)
         if finished and finished[0].sub.shape[0] >= 2:
@@ -344,11 +396,11 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 perm0 = torch.unique(torch.cat([torch.searchsorted(sub, finished[0].sub), perm0]))
             ci, cs = _bruteforce_knn(xs[perm0], min(k_cand, perm0.shape[0] - 1), mt)
             if ci.shape[1] > 0:
-                keep = _select_heuristic(xs[perm0], ci, cs, M, mt, alpha=alpha)
+                keep = select(xsel[perm0], ci, cs, M, mt, alpha=alpha)
                 src = perm0[torch.arange(perm0.shape[0], device=dev)[:, None].expand_as(ci)[keep]]
                 dst = perm0[ci[keep]]
                 w = cs[keep]
-                G.add_links(xs, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
+                G.add_links(xsel, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
             inserted[perm0] = True
         rest = torch.nonzero(~inserted).flatten()
         rest = rest[torch.randperm(rest.shape[0], generator=gen).to(dev)]
@@ -384,7 +436,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 o = torch.argsort(sim, dim=1, descending=True, stable=True)
                 ids, sim = torch.gather(ids, 1, o), torch.gather(sim, 1, o)
             ids = ids.masked_fill(~torch.isfinite(sim), -1)
-            keep = _select_heuristic(xs, ids, sim, M, mt, alpha=alpha)
+            keep = select(xsel, ids, sim, M, mt, alpha=alpha)
             src = batch[:, None].expand_as(ids)[keep]
             dst = ids[keep]
             w = sim[keep]
@@ -392,7 +444,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 G.adj[batch] = -1
                 G.sim[batch] = -float("inf")
                 G.deg[batch] = 0
-            G.add_links(xs, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
+            G.add_links(xsel, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
             inserted[batch] = True
 
         pos = 0
@@ -420,7 +472,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
 
 
 @torch.no_grad()
-def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02) -> HnswCsr:
+def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch") -> HnswCsr:
     """High-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3, p. 6): storage drops from ~2M links per node
     to ~m_low while the few hub nodes that most searches pass through keep their full lists.
 
@@ -432,7 +484,9 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
       * for every kept link v -> u the reverse link u -> v is offered as well and every node may hold up to 2M links in
         total, overflowing lists being shrunk with the same heuristic (paper: "all nodes establish bidirectional edges up
         to the maximum threshold M; only the number of outgoing selections of low-degree nodes is restricted").
-    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device."""
+    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device; ``selector`` as
+    in build_graph_gpu."""
+    _selector_fn(selector)
     n = g.ntotal
     if n == 0 or m_low >= 2 * M:
         return g
@@ -460,11 +514,12 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
     for b0 in range(0, src.shape[0], 1 << 20):
         a, b = x[src[b0 : b0 + (1 << 20)]].float(), x[dst[b0 : b0 + (1 << 20)]].float()
         w[b0 : b0 + (1 << 20)] = (a * b).sum(1) if mt == METRIC_INNER_PRODUCT else -((a - b) ** 2).sum(1)
-    G = _LevelGraph(torch.arange(n, device=dev), cap)
+    G = _LevelGraph(torch.arange(n, device=dev), cap, selector)
+    xsel = _padded_table(x) if selector == "kernel" else x
     step = 1 << 21  # bound the temporaries of add_links
     for b0 in range(0, src.shape[0], step):
         s_, d_, w_ = src[b0 : b0 + step], dst[b0 : b0 + step], w[b0 : b0 + step]
-        G.add_links(x, torch.cat([s_, d_]), torch.cat([d_, s_]), torch.cat([w_, w_]), mt)
+        G.add_links(xsel, torch.cat([s_, d_]), torch.cat([d_, s_]), torch.cat([w_, w_]), mt)
     new0 = G.adj.cpu().numpy()
     # reassemble: level 0 replaced, upper levels copied
     nlev = g.levels.astype(np.int64)
