@@ -266,6 +266,35 @@ int lm_topk_merge(const int64_t *d_in_ids, const float *d_in_dist, int32_t S, in
 int lm_select_neighbors(const void *d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric,
                         const int32_t *d_cand, const float *d_dist, int64_t n, int32_t K, int32_t m, float alpha,
                         uint8_t *d_keep, void *stream);
+/* Index build time: the product quantiser that lm_pq_attach / lm_pq_attach_chunked take, made by the library -- nearest-centroid
+ * assignment (lm_pq_encode) and Lloyd iterations over a sample (lm_pq_train); the role of DiskANN's generate_pq_pivots /
+ * generate_pq_data_from_pivots behind diskann_backend.py:105-111 (leann_amd/pq.py holds the torch forms).
+ *   d_x            n (or s) rows of fp32 or fp16 with row stride ld elements (ld >= d): a raw [n][d] array and the zero-padded
+ *                  stored-embedding table are both passed as they are;
+ *   chunk_offsets  HOST array of m + 1 ints: chunk j covers dimensions [chunk_offsets[j], chunk_offsets[j+1]), lengths may differ
+ *                  and may be 0, chunk_offsets[m] <= d; NULL = the uniform layout, m chunks of d / m;
+ *   d_codebooks    lm_pq_attach's layout exactly: chunk j's 256 centroids x len_j floats at float offset 256 * chunk_offsets[j]
+ *                  (uniform: [m][256][d/m]); lm_pq_train reads the initial centroids from it and writes the trained ones to it;
+ *   d_codes        out, [n][m] bytes.
+ * The contract is the arithmetic.  Assignment (both entry points), chunk j of row v, ALWAYS squared L2 whatever the index metric (as in
+ * faiss and DiskANN):  dist_c = acc after { acc = 0.0f; for t = 0 .. len_j - 1: diff = x[lo + t] - cb[c][t]; acc = fmaf(diff, diff, acc) }
+ * for c = 0 .. 255 -- oracle/lm_oracle_pq.c:orc_pq_lut's L2 form with the row as the query, fp16 rows widened first (exact) --; then
+ * { code = 0; best = +inf; for c ascending: if (dist_c < best) { best = dist_c; code = c; } }: ties go to the lowest c, a NaN distance never
+ * wins, a chunk whose distances are all NaN or whose length is 0 gets code 0.
+ * Update (lm_pq_train, after each assignment): for every (j, c) with count > 0 and every coordinate t,
+ * { sum = 0.0f; for rows v ASCENDING with code[v][j] == c: sum = sum + x[v][lo + t]; }  cb[c][t] = sum / (float)count -- IEEE fp32, no
+ * contraction; a centroid with count == 0 stays as it was.  `iters` rounds of assignment + update; iters == 0 leaves the codebooks
+ * untouched.  No floating-point atomics: the trained codebooks are a function of the input bits alone.
+ * LM_EINVAL (before anything is launched): a NULL buffer with n > 0, an unknown dtype, ld < d, m < 1 or m > 4096, uniform layout with
+ * d % m != 0, chunk_offsets[0] != 0, decreasing offsets, chunk_offsets[m] > d, a chunk longer than LM_PQ_MAX_SUB (a chunk's 256
+ * centroids then fit in 64 KB of LDS), negative n / s / iters, workspace_bytes < lm_pq_train_workspace_bytes(s, d, m).
+ * n == 0 / s == 0: LM_OK.  m % 4 is NOT required here (lm_pq_attach requires it: padding the code rows stays the caller's job). */
+#define LM_PQ_MAX_SUB 64
+int lm_pq_encode(const void *d_x, int32_t dtype, int64_t n, int32_t ld, int32_t d, int32_t m, const int32_t *chunk_offsets,
+                 const float *d_codebooks, uint8_t *d_codes, void *stream);
+int lm_pq_train(const void *d_x, int32_t dtype, int64_t s, int32_t ld, int32_t d, int32_t m, const int32_t *chunk_offsets,
+                int32_t iters, float *d_codebooks, void *d_workspace, size_t workspace_bytes, void *stream);
+size_t lm_pq_train_workspace_bytes(int64_t s, int32_t d, int32_t m);
 
 /* ---- fused encoder elementwise ops ---------------------------------------------------------------
  * out = LayerNorm(x + residual) * gamma + beta over the last dim; fp16 in/out, fp32 arithmetic;

@@ -18,6 +18,7 @@ LM_OK, LM_EINVAL, LM_ENOENT, LM_EFORMAT, LM_EHIP, LM_ESTATE, LM_EPROVIDER = 0, -
 METRIC_INNER_PRODUCT, METRIC_L2 = 0, 1
 DTYPE_F32, DTYPE_F16 = 0, 1
 SELECT_MAX_K = 512  # include/leann_mi355x.h: LM_SELECT_MAX_K
+PQ_MAX_SUB = 64  # include/leann_mi355x.h: LM_PQ_MAX_SUB
 
 
 class LeannMi355xError(RuntimeError):
@@ -107,7 +108,7 @@ EXPORTED_SYMBOLS = [
     "lm_index_attach_table", "lm_index_set_provider", "lm_index_set_hub_cache", "lm_index_set_stream",
     "lm_search_params_default", "lm_index_search", "lm_index_search_device",
     "lm_index_get_stats", "lm_index_set_profiling", "lm_index_set_option", "lm_index_get_option", "lm_index_event_overhead_us",
-    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors",
+    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
     "lm_pq_attach", "lm_pq_attach_chunked", "lm_pq_search_params_default", "lm_pq_batch_search", "lm_pq_batch_search_device",
     "lm_add_layernorm_f16", "lm_attn_varlen_hd32_f16", "lm_attn_varlen_f16", "lm_embed_layernorm_f16", "lm_meanpool_varlen_f16",
     "lm_layer_tail_h384_f16", "lm_layer_tail_pack_h384", "lm_qkv_h384_f16", "lm_qkv_attn_h384_f16", "lm_h384_first_half_form", "lm_qkv_pack_h384", "lm_gemm_ws_h384_f16", "lm_gemm_f16", "lm_pack_tokens",
@@ -160,6 +161,10 @@ def load() -> C.CDLL:
     lib.lm_dist_gather.argtypes = [vp, i32, i32, i32, vp, vp, vp, i64, vp, vp]
     lib.lm_topk_merge.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.lm_select_neighbors.argtypes = [vp, i32, i64, i32, i32, vp, vp, i64, i32, i32, C.c_float, vp, vp]
+    lib.lm_pq_encode.argtypes = [vp, i32, i64, i32, i32, i32, vp, vp, vp, vp]
+    lib.lm_pq_train.argtypes = [vp, i32, i64, i32, i32, i32, vp, i32, vp, vp, C.c_size_t, vp]
+    lib.lm_pq_train_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.lm_pq_train_workspace_bytes.restype = C.c_size_t
     lib.lm_pq_attach.argtypes = [vp, i32, vp, vp, i64]
     lib.lm_pq_attach_chunked.argtypes = [vp, i32, vp, vp, vp, i64]
     lib.lm_pq_search_params_default.argtypes = [C.POINTER(PqSearchParams)]

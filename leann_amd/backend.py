@@ -57,6 +57,28 @@ def hub_nodes(g: HnswCsr, ratio: float) -> np.ndarray:
     return np.sort(order[:k]).astype(np.int32)
 
 
+def _make_pq(x, m: int, gpu_pq_kernel: bool = False):
+    """The product quantiser of both builders: (codebooks [m, 256, d/m], codes [N, m]) as host tensors from the host tensor ``x`` [N, d].
+    Build parameter ``gpu_pq_kernel`` (bool, default False): the embeddings go to the device and the library's kernels (lm_pq_train /
+    lm_pq_encode through leann_amd.pq) train and encode; by default the torch pair train_pq / encode_pq does, as it always has."""
+    from .pq import encode_pq, encode_pq_kernel, train_pq, train_pq_kernel
+
+    if not gpu_pq_kernel:
+        cb = train_pq(x, m, seed=0)
+        return cb, encode_pq(x, cb)
+    _lib.require_gpu()
+    xd = x.to(_pq_kernel_device())
+    cb = train_pq_kernel(xd, m, seed=0)
+    return cb.cpu(), encode_pq_kernel(xd, cb).cpu()
+
+
+def _pq_kernel_device():
+    """Where gpu_pq_kernel puts the embeddings: the current HIP device."""
+    import torch
+
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 @register_backend("mi355x")
 class Mi355xBackend(LeannBackendFactoryInterface):
     @staticmethod
@@ -70,7 +92,8 @@ class Mi355xBackend(LeannBackendFactoryInterface):
 
 class Mi355xBuilder(LeannBackendBuilderInterface):
     """Mirror of HNSWBuilder (hnsw_backend.py:49-117): same kwargs and defaults, writes the same
-    compact-CSR ``<stem>.index`` file (pruned when ``is_recompute``)."""
+    compact-CSR ``<stem>.index`` file (pruned when ``is_recompute``).  ``pq_bytes`` > 0 adds ``<stem>_pq.npz`` for the two-level search;
+    ``gpu_pq_kernel`` (bool, default False) makes it with the library's kernels (_make_pq)."""
 
     def __init__(self, **kwargs):
         self.build_params = kwargs.copy()
@@ -104,11 +127,9 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         if pq_bytes > 0:  # optional product quantiser for the two-level search (prune_ratio), cf. the fork's PQ pruning
             import torch
 
-            from .pq import encode_pq, train_pq
-
             x = torch.from_numpy(np.ascontiguousarray(data))
-            cb = train_pq(x, pq_bytes, seed=0)
-            np.savez(path.parent / f"{path.stem}_pq.npz", codebooks=cb.numpy(), codes=encode_pq(x, cb).numpy())
+            cb, codes = _make_pq(x, pq_bytes, gpu_pq_kernel=bool(self.build_params.get("gpu_pq_kernel", False)))
+            np.savez(path.parent / f"{path.stem}_pq.npz", codebooks=cb.numpy(), codes=codes.numpy())
 
 
     def _build_graph(self, data: np.ndarray, metric: str):
@@ -475,7 +496,8 @@ class Mi355xDiskannBuilder(LeannBackendBuilderInterface):
     ``graph_degree``, ``search_memory_maximum`` (PQ budget), ``distance_metric``, ``num_threads``.
     Writes ``<stem>.index`` (flat graph in the compact-CSR container, entry = medoid, embeddings kept
     unless ``is_recompute``) and ``<stem>_pq.npz`` (codebooks + codes: the role of
-    ``_pq_pivots.bin`` / ``_pq_compressed.bin``, whose real layouts live in the absent fork)."""
+    ``_pq_pivots.bin`` / ``_pq_compressed.bin``, whose real layouts live in the absent fork).  ``gpu_pq_kernel`` (bool, default False):
+    the quantiser is made by the library's kernels (_make_pq) instead of the torch pair."""
 
     def __init__(self, **kwargs):
         self.build_params = kwargs.copy()
@@ -484,7 +506,7 @@ class Mi355xDiskannBuilder(LeannBackendBuilderInterface):
         import torch
 
         from .hnsw_builder import build_hnsw
-        from .pq import encode_pq, flat_graph, train_pq
+        from .pq import flat_graph
 
         path = Path(index_path)
         path.parent.mkdir(parents=True, exist_ok=True)
@@ -507,8 +529,7 @@ class Mi355xDiskannBuilder(LeannBackendBuilderInterface):
         write_index(path.parent / f"{path.stem}.index", fg, prune_embeddings=bool(bk.get("is_recompute", False)))
         m = int(bk.get("pq_bytes") or pq_bytes_for_budget(data.shape[0], data.shape[1], bk.get("search_memory_maximum")))
         x = torch.from_numpy(data)
-        cb = train_pq(x, m, seed=0)
-        codes = encode_pq(x, cb)
+        cb, codes = _make_pq(x, m, gpu_pq_kernel=bool(bk.get("gpu_pq_kernel", False)))
         np.savez(path.parent / f"{path.stem}_pq.npz", codebooks=cb.numpy(), codes=codes.numpy())
 
 

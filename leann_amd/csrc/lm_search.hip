@@ -1056,4 +1056,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 
 #include "lm_pq_impl.h"
 #include "lm_select_impl.h"
+#include "lm_pq_build_impl.h"
 

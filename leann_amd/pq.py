@@ -3,7 +3,8 @@
 DiskANN keeps PQ-compressed vectors in memory and traverses on PQ distances
 (diskann_backend.py:444-449; compression budget `search_memory_maximum` ~ N*D*4/10 bytes,
 :105-111 -> m ~ D*4/10 bytes per vector).  Training (k-means per sub-space) and encoding are
-torch ops (any device); the traversal kernel lives in csrc/lm_pq_impl.h.
+torch ops (any device); the traversal kernel lives in csrc/lm_pq_impl.h.  ``train_pq_kernel`` / ``encode_pq_kernel`` are the same
+two steps on the library's kernels (lm_pq_train / lm_pq_encode, csrc/lm_pq_build_impl.h): opt-in, fully specified arithmetic.
 """
 
 from __future__ import annotations
@@ -51,6 +52,105 @@ def encode_pq(x: torch.Tensor, codebooks: torch.Tensor, block: int = 65536) -> t
         d2 = -2 * xs @ codebooks.transpose(1, 2) + cbn[:, None, :]
         out[b0 : b0 + block] = d2.argmin(-1).transpose(0, 1).to(torch.uint8)
     return out
+
+
+def _kernel_rows(x: torch.Tensor):
+    """x as the library takes it: fp32 or fp16 rows with unit element stride -> (tensor, dtype code, ld, stream)."""
+    from . import _lib
+
+    if x.dim() != 2:
+        raise ValueError("x must be [N, d]")
+    if x.dtype not in (torch.float32, torch.float16):
+        x = x.float()
+    if x.shape[0] <= 1 or x.shape[1] == 0 or x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()  # (anything but rows of unit element stride at a row stride >= d)
+    ld = x.stride(0) if x.shape[0] > 1 and x.shape[1] > 0 else x.shape[1]
+    stream = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else None
+    return x, (_lib.DTYPE_F16 if x.dtype == torch.float16 else _lib.DTYPE_F32), int(ld), stream
+
+
+def _kernel_chunks(chunk_offsets):
+    """chunk_offsets (None = uniform) -> (host int32 array or None, its address or None)."""
+    if chunk_offsets is None:
+        return None, None
+    off = np.ascontiguousarray(np.asarray(chunk_offsets), dtype=np.int32)
+    if off.ndim != 1 or off.shape[0] < 2:
+        raise ValueError("chunk_offsets must hold m + 1 offsets")
+    return off, off.ctypes.data
+
+
+@torch.no_grad()
+def encode_pq_kernel(x: torch.Tensor, codebooks: torch.Tensor, chunk_offsets=None) -> torch.Tensor:
+    """encode_pq on the library's kernel (lm_pq_encode) -> codes [N, m] uint8 on x's device.  ``x``: fp32 or fp16 rows, possibly a
+    column slice of a wider table (the row stride is passed on).  ``codebooks``: [m, 256, d/m], or -- with ``chunk_offsets`` (m + 1 ints,
+    the layout of lm_pq_attach_chunked) -- the flat array of 256 * chunk_offsets[m] floats; columns from chunk_offsets[m] on carry no code.
+    The arithmetic is the header's: sequential-fmaf squared L2 as the search's lookup table computes it, ties to the lowest centroid."""
+    from . import _lib
+
+    x, dt, ld, stream = _kernel_rows(x)
+    n, d = x.shape
+    off, off_p = _kernel_chunks(chunk_offsets)
+    cb = codebooks.to(device=x.device, dtype=torch.float32).contiguous()
+    if off is None:
+        if cb.dim() != 3 or cb.shape[1] != 256:
+            raise ValueError("codebooks must be [m, 256, d/m]")
+        m = int(cb.shape[0])
+        if m * cb.shape[2] != d:
+            raise ValueError("codebooks [m, 256, dsub] need m * dsub == d")
+    else:
+        m = int(off.shape[0]) - 1
+        if cb.numel() != 256 * max(int(off[-1]), 0):
+            raise ValueError("chunked codebooks must hold 256 * chunk_offsets[m] floats")
+    codes = torch.empty((n, m), dtype=torch.uint8, device=x.device)
+    rc = _lib.load().lm_pq_encode(x.data_ptr(), dt, n, ld, d, m, off_p, cb.data_ptr(), codes.data_ptr(), stream)
+    _lib.check(rc, "lm_pq_encode")
+    return codes
+
+
+@torch.no_grad()
+def lloyd_kernel(xs: torch.Tensor, codebooks: torch.Tensor, iters: int, chunk_offsets=None) -> torch.Tensor:
+    """``iters`` Lloyd iterations (lm_pq_train) over the rows ``xs`` from the centroids ``codebooks`` (layouts as encode_pq_kernel);
+    returns the trained codebooks as a new tensor of the same shape."""
+    from . import _lib
+
+    xs, dt, ld, stream = _kernel_rows(xs)
+    s, d = xs.shape
+    off, off_p = _kernel_chunks(chunk_offsets)
+    cb = codebooks.to(device=xs.device, dtype=torch.float32).contiguous().clone()
+    m = int(cb.shape[0]) if off is None else int(off.shape[0]) - 1
+    if off is None and (cb.dim() != 3 or cb.shape[1] != 256 or m * cb.shape[2] != d):
+        raise ValueError("codebooks must be [m, 256, d/m]")
+    if off is not None and cb.numel() != 256 * max(int(off[-1]), 0):
+        raise ValueError("chunked codebooks must hold 256 * chunk_offsets[m] floats")
+    lib = _lib.load()
+    nbytes = int(lib.lm_pq_train_workspace_bytes(s, d, m))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xs.device)
+    rc = lib.lm_pq_train(xs.data_ptr(), dt, s, ld, d, m, off_p, int(iters), cb.data_ptr(), ws.data_ptr(), nbytes, stream)
+    _lib.check(rc, "lm_pq_train")
+    return cb
+
+
+@torch.no_grad()
+def train_pq_kernel(x: torch.Tensor, m: int, iters: int = 12, sample: int = 131072, seed: int = 0) -> torch.Tensor:
+    """train_pq on the library's kernels (lm_pq_train): the sample and the 256 initial rows are drawn with exactly train_pq's generator
+    calls, so both forms start from the same centroids; the iterations then run with the header's arithmetic (sums in ascending row
+    order, no atomics: the result is a function of the input bits).  Returns codebooks [m, 256, d/m] float32 on x's device."""
+    n, d = x.shape
+    if m < 1 or d % m:
+        raise ValueError("m must divide d")
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    idx = torch.randperm(n, generator=g)[: min(n, sample)].to(x.device)
+    xs = x[idx]
+    if xs.dtype not in (torch.float32, torch.float16):
+        xs = xs.float()
+    s = xs.shape[0]
+    init = torch.randperm(s, generator=g)[:256].to(x.device)
+    if s < 256:
+        init = torch.arange(256, device=x.device) % max(s, 1)
+    if s == 0:
+        return torch.zeros((m, 256, d // m), dtype=torch.float32, device=x.device)
+    cb = xs[init].float().view(256, m, d // m).transpose(0, 1).contiguous()  # [m, 256, dsub]
+    return lloyd_kernel(xs, cb, iters)
 
 
 def flat_graph(g: HnswCsr, x) -> HnswCsr:
