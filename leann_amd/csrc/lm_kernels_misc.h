@@ -102,11 +102,14 @@ __global__ __launch_bounds__(256) void k_dist_pairs(const void* table, const flo
     if (lane16 == 0) out[p] = d;
 }
 
-// per-query merge of S shard lists (one 64-lane block per query, LDS bitonic)
+// per-query merge of S shard lists (one 64-lane block per query, LDS bitonic).  Order: (internal distance, id) -- make_key's total order,
+// where -0 == +0 --, then the input slot, so the result is a function of the inputs alone.  The output distance is the input's own
+// word (oracle/lm_oracle.c:orc_merge_topk copies it too): the sort carries the slot, not a distance rebuilt from the key, which would
+// turn an inner-product +0 into -0 and an L2 -0 into +0.
 __global__ __launch_bounds__(64) void k_topk_merge(const int64_t* in_ids, const float* in_dist, int S, int B, int k,
                                                    int metric, int P2, int64_t* out_ids, float* out_dist) {
     extern __shared__ __align__(16) unsigned char smem[];
-    uint64_t* keys = (uint64_t*)smem;          // P2 : (dist, slot)
+    uint64_t* keys = (uint64_t*)smem;          // P2 : (ordered 32-bit distance, input slot s * k + j); KEY_NONE = empty
     const int q = blockIdx.x, tid = threadIdx.x;
     const int tot = S * k;
     // key = (internal dist, id) cannot hold 63-bit ids: sort by (dist, id) with a 2-word compare
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(64) void k_topk_merge(const int64_t* in_ids, const 
                 keys[i] = KEY_NONE;
                 ids[i] = INT64_MAX;
             } else {
-                keys[i] = make_key(d, 0) >> 32;  // ordered 32-bit distance
+                keys[i] = (make_key(d, 0) & 0xFFFFFFFF00000000ull) | (uint32_t)i;  // (the ordered distance is never 0xFFFFFFFF: NaN -> +inf)
                 ids[i] = id;
             }
         } else {
@@ -137,7 +140,8 @@ __global__ __launch_bounds__(64) void k_topk_merge(const int64_t* in_ids, const 
                 if (ixj > i) {
                     uint64_t x = keys[i], y = keys[ixj];
                     int64_t xi = ids[i], yi = ids[ixj];
-                    bool gt = x > y || (x == y && xi > yi);
+                    uint32_t xd = (uint32_t)(x >> 32), yd = (uint32_t)(y >> 32);
+                    bool gt = xd > yd || (xd == yd && (xi > yi || (xi == yi && x > y)));
                     bool up = (i & k2) == 0;
                     if (gt == up) {
                         keys[i] = y; keys[ixj] = x;
@@ -153,9 +157,9 @@ __global__ __launch_bounds__(64) void k_topk_merge(const int64_t* in_ids, const 
             out_ids[dst] = -1;
             out_dist[dst] = metric == LM_METRIC_L2 ? __builtin_inff() : -__builtin_inff();
         } else {
-            float d = key_dist(keys[i] << 32);
+            int slot = (int)(uint32_t)keys[i];
             out_ids[dst] = ids[i];
-            out_dist[dst] = metric == LM_METRIC_L2 ? d : -d;
+            out_dist[dst] = in_dist[((size_t)(slot / k) * B + q) * k + slot % k];
         }
     }
 }

@@ -141,11 +141,10 @@ def case_encode_vs_restatement():
 CASES["encode_vs_restatement"] = case_encode_vs_restatement
 
 
-def case_encode_ties_and_nan():
-    """Exact ties go to the lowest index; a NaN coordinate in a row makes every distance of that chunk NaN (code 0) and leaves the other
-    chunks alone; a NaN coordinate in a centroid removes that centroid only; +inf distances never win against the initial +inf."""
-    from tests.pq_ref_util import lut_argmin_codes, ref_encode
-
+def _ties_and_nan_inputs():
+    """The four configurations of case_encode_ties_and_nan: (f16, d, m, off, x, cb, j0, j1).  Chunk j0 holds seven distinct centroids, each
+    repeated; row 5 has a NaN in chunk j0; centroid 0 of chunk j1 is row 7's chunk with a NaN, centroids 3 and 9 that chunk without it;
+    row 8 has +inf in chunk j1."""
     for f16 in (False, True):
         for (d, m, off) in ((32, 8, None), (24, 4, [0, 8, 8, 12, 24])):
             n = 90
@@ -167,13 +166,22 @@ def case_encode_ties_and_nan():
             blk1[3] = x[7, lo1 : lo1 + ln1].astype(np.float32)  # centroid 3 is that chunk without the NaN
             blk1[9] = blk1[3]
             x[8, lo1] = np.inf                                  # row 8: inf - finite = inf in every distance of chunk j1 -> code 0
-            got = _kernel_encode(x, d, cb, off)
-            exp = ref_encode(REF, x, d, cb, off)
-            pin = lut_argmin_codes(x, d, cb, off)
-            ok = np.array_equal(got, exp) and np.array_equal(got, pin)
-            ok = ok and int(got[:, j0].max()) < 7 and got[5, j0] == 0 and got[7, j1] == 3 and got[8, j1] == 0
-            print(f"ties/NaN d={d} m={m} chunked={off is not None} f16={f16}: {'ok' if ok else 'MISMATCH'}", flush=True)
-            assert ok
+            yield f16, d, m, off, x, cb, j0, j1
+
+
+def case_encode_ties_and_nan():
+    """Exact ties go to the lowest index; a NaN coordinate in a row makes every distance of that chunk NaN (code 0) and leaves the other
+    chunks alone; a NaN coordinate in a centroid removes that centroid only; +inf distances never win against the initial +inf."""
+    from tests.pq_ref_util import lut_argmin_codes, ref_encode
+
+    for f16, d, m, off, x, cb, j0, j1 in _ties_and_nan_inputs():
+        got = _kernel_encode(x, d, cb, off)
+        exp = ref_encode(REF, x, d, cb, off)
+        pin = lut_argmin_codes(x, d, cb, off)
+        ok = np.array_equal(got, exp) and np.array_equal(got, pin)
+        ok = ok and int(got[:, j0].max()) < 7 and got[5, j0] == 0 and got[7, j1] == 3 and got[8, j1] == 0
+        print(f"ties/NaN d={d} m={m} chunked={off is not None} f16={f16}: {'ok' if ok else 'MISMATCH'}", flush=True)
+        assert ok
 
 
 CASES["encode_ties_and_nan"] = case_encode_ties_and_nan
@@ -193,27 +201,35 @@ def _counts(codes):
     return np.stack([np.bincount(codes[:, j], minlength=256) for j in range(codes.shape[1])])
 
 
+TRAIN_SHAPES = [
+    # (s, d, ld, m, chunk offsets, fp16, kind)
+    (700, 32, 32, 8, None, False, "real"),
+    (100, 32, 64, 4, None, False, "real"),   # s < 256: init = arange(256) % s
+    (700, 32, 32, 16, None, True, "real"),
+    (450, 24, 24, 2, None, False, "int"),    # length 12
+    (520, 130, 192, 8, [0, 3, 3, 10, 11, 27, 27, 59, 123], False, "real"),
+    (300, 130, 130, 8, [0, 3, 3, 10, 11, 27, 27, 59, 123], True, "int"),
+    (0, 32, 32, 8, None, False, "real"),
+]
+
+
+def _train_input(i, s, d, ld, m, off, f16, kind):
+    """The sample and the initial centroids of train shape number i: 256 of its rows (s < 256: arange(256) % s, train_pq's rule)."""
+    x = _data(s, d, ld, 500 + i, kind, f16)
+    rng = np.random.default_rng(600 + i)
+    rows = (np.arange(256) % s if 0 < s < 256 else rng.permutation(s)[:256]) if s else np.zeros(256, np.int64)
+    init = _init_rows(x, d, m, off, rows) if s else np.zeros((m, 256, d // m), np.float32)
+    return x, init
+
+
 def case_train_vs_restatement():
     """lm_pq_train against the restatement, bit for bit: iters 0 / 1 / 5, fewer than 256 rows (repeated centroids that never receive a
     row), clusters that lose all their rows in a later iteration, fp16 input, padded rows, the chunked layout."""
     from tests.pq_ref_util import ref_encode, ref_train
 
-    shapes = [
-        # (s, d, ld, m, chunk offsets, fp16, kind)
-        (700, 32, 32, 8, None, False, "real"),
-        (100, 32, 64, 4, None, False, "real"),   # s < 256: init = arange(256) % s
-        (700, 32, 32, 16, None, True, "real"),
-        (450, 24, 24, 2, None, False, "int"),    # length 12
-        (520, 130, 192, 8, [0, 3, 3, 10, 11, 27, 27, 59, 123], False, "real"),
-        (300, 130, 130, 8, [0, 3, 3, 10, 11, 27, 27, 59, 123], True, "int"),
-        (0, 32, 32, 8, None, False, "real"),
-    ]
     emptied = 0
-    for i, (s, d, ld, m, off, f16, kind) in enumerate(shapes):
-        x = _data(s, d, ld, 500 + i, kind, f16)
-        rng = np.random.default_rng(600 + i)
-        rows = (np.arange(256) % s if 0 < s < 256 else rng.permutation(s)[:256]) if s else np.zeros(256, np.int64)
-        init = _init_rows(x, d, m, off, rows) if s else np.zeros((m, 256, d // m), np.float32)
+    for i, (s, d, ld, m, off, f16, kind) in enumerate(TRAIN_SHAPES):
+        x, init = _train_input(i, s, d, ld, m, off, f16, kind)
         for iters in (0, 1, 5):
             got = _kernel_train(x, d, init, iters, off)
             exp = ref_train(REF, x, d, init, iters, off)
@@ -382,22 +398,31 @@ def case_builder_wiring():
 CASES["builder_wiring"] = case_builder_wiring
 
 
-def case_argument_checking():
-    """Every argument the header rejects returns LM_EINVAL (ValueError through _lib.check) and launches nothing: the output buffers keep
-    their fill.  n == 0 / s == 0 / iters == 0 are fine."""
+class _HostBuf:
+    """A buffer of the emulated world, where 'device' memory is host memory: .ptr for the ABI, .host() to read it back."""
+
+    def __init__(self, a):
+        self.a = a
+        self.ptr = a.ctypes.data
+
+    def host(self):
+        return self.a
+
+
+def argument_envelope(buf, ref):
+    """The library-level half of case_argument_checking over buffers made by `buf(array)` (an object with .ptr and .host()): host
+    memory for the emulated library, device memory on the MI355X (tests/test_gpu_pq_build_edges.py runs this very function)."""
     import pytest
-    import torch
 
     from leann_amd import _lib
-    from leann_amd.pq import encode_pq_kernel, train_pq_kernel
 
     lib = _lib.load()
-    x = np.zeros((8, 16), np.float32)
-    cb = np.full((4, 256, 4), 0.25, np.float32)
-    good = dict(x=x.ctypes.data, dtype=0, n=8, ld=16, d=16, m=4, off=None, cb=cb.ctypes.data, iters=2)
+    x = buf(np.zeros((8, 16), np.float32))
+    cb = buf(np.full((4, 256, 4), 0.25, np.float32))
+    good = dict(x=x.ptr, dtype=0, n=8, ld=16, d=16, m=4, off=None, cb=cb.ptr, iters=2)
     offs = {}
 
-    def offp(v):
+    def offp(v):  # chunk_offsets is a host array in both worlds
         if v is None:
             return None
         offs["keep"] = np.ascontiguousarray(v, np.int32)
@@ -405,46 +430,58 @@ def case_argument_checking():
 
     def enc(out, **over):
         a = dict(good, **over)
-        return lib.lm_pq_encode(a["x"], a["dtype"], a["n"], a["ld"], a["d"], a["m"], offp(a["off"]), a["cb"], a.get("codes", out.ctypes.data), None)
+        return lib.lm_pq_encode(a["x"], a["dtype"], a["n"], a["ld"], a["d"], a["m"], offp(a["off"]), a["cb"], a.get("codes", out.ptr), None)
 
     def trn(wsp, **over):
         a = dict(good, **over)
-        return lib.lm_pq_train(a["x"], a["dtype"], a["n"], a["ld"], a["d"], a["m"], offp(a["off"]), a["iters"], a["cb"], a.get("ws", wsp.ctypes.data),
-                               a.get("wsb", wsp.nbytes), None)
+        return lib.lm_pq_train(a["x"], a["dtype"], a["n"], a["ld"], a["d"], a["m"], offp(a["off"]), a["iters"], a["cb"], a.get("ws", wsp.ptr),
+                               a.get("wsb", wsp.host().nbytes), None)
 
     shape_bad = [dict(dtype=2), dict(dtype=-1), dict(ld=15), dict(m=0), dict(m=-2), dict(m=4097), dict(m=3), dict(n=-1),
                  dict(off=[1, 4, 8, 12, 16]), dict(off=[0, 8, 4, 12, 16]), dict(off=[0, 4, 8, 12, 17]), dict(x=None), dict(cb=None),
                  dict(m=1, d=80, ld=80),                                  # uniform chunk of 80 > LM_PQ_MAX_SUB
                  dict(m=2, d=80, ld=80, off=[0, 65, 80])]                 # chunked: 65 > LM_PQ_MAX_SUB
-    codes = np.full((8, 4), 0xEE, np.uint8)
+    codes = buf(np.full((8, 4), 0xEE, np.uint8))
     need = int(lib.lm_pq_train_workspace_bytes(8, 16, 4))
     assert need >= 8 * 4
-    ws = np.full(need, 0xEE, np.uint8)
-    cb0 = cb.tobytes()
+    ws = buf(np.full(need, 0xEE, np.uint8))
+    cb0 = cb.host().tobytes()
     for over in shape_bad + [dict(codes=None)]:
         with pytest.raises(ValueError):
             _lib.check(enc(codes, **over), "lm_pq_encode")
-        assert (codes == 0xEE).all(), over
+        assert (codes.host() == 0xEE).all(), over
     for over in shape_bad + [dict(iters=-1), dict(ws=None), dict(wsb=need - 1), dict(wsb=0)]:
         with pytest.raises(ValueError):
             _lib.check(trn(ws, **over), "lm_pq_train")
-        assert (ws == 0xEE).all() and cb.tobytes() == cb0, over
+        assert (ws.host() == 0xEE).all() and cb.host().tobytes() == cb0, over
     assert _lib.last_error()
     # nothing to do: fine, and still nothing written (NULL buffers are allowed when there are no rows)
     _lib.check(enc(codes, n=0, x=None, cb=None, codes=None))
     _lib.check(trn(ws, n=0, x=None, cb=None, ws=None, wsb=0))
     _lib.check(trn(ws, iters=0))
-    assert (codes == 0xEE).all() and (ws == 0xEE).all() and cb.tobytes() == cb0
+    assert (codes.host() == 0xEE).all() and (ws.host() == 0xEE).all() and cb.host().tobytes() == cb0
     # m % 4 is not required here; a well-formed call writes every code
     cb3 = np.ascontiguousarray(np.random.default_rng(0).standard_normal((3, 256, 4)), np.float32)
     x12 = np.ascontiguousarray(np.random.default_rng(1).standard_normal((8, 12)), np.float32)
-    c3 = np.full((8, 3), 0xEE, np.uint8)
-    _lib.check(lib.lm_pq_encode(x12.ctypes.data, 0, 8, 12, 12, 3, None, cb3.ctypes.data, c3.ctypes.data, None))
+    c3 = buf(np.full((8, 3), 0xEE, np.uint8))
+    bx12, bcb3 = buf(x12), buf(cb3)
+    _lib.check(lib.lm_pq_encode(bx12.ptr, 0, 8, 12, 12, 3, None, bcb3.ptr, c3.ptr, None))
     from tests.pq_ref_util import ref_encode
 
-    assert np.array_equal(c3, ref_encode(REF, x12, 12, cb3))
+    assert np.array_equal(c3.host(), ref_encode(ref, x12, 12, cb3))
     _lib.check(enc(codes))
-    assert (codes == 0).all()  # every centroid equal: the lowest index
+    assert (codes.host() == 0).all()  # every centroid equal: the lowest index
+
+
+def case_argument_checking():
+    """Every argument the header rejects returns LM_EINVAL (ValueError through _lib.check) and launches nothing: the output buffers keep
+    their fill.  n == 0 / s == 0 / iters == 0 are fine."""
+    import pytest
+    import torch
+
+    from leann_amd.pq import encode_pq_kernel, train_pq_kernel
+
+    argument_envelope(_HostBuf, REF)
     print("argument checking: ok", flush=True)
     # the wrappers raise ValueError for the same envelope
     xt = torch.zeros((10, 16))

@@ -618,3 +618,201 @@ def test_random_degenerate_graphs_match_oracle(env):
             assert np.array_equal(l, oi) and np.array_equal(d.view(np.uint32), od.view(np.uint32)), (seed, mode, n, k, ef, beam)
             assert (st["ndis"], st["nexpand"], st["nrounds"]) == (ost["ndis"], ost["nexpand"], ost["nrounds"]), (seed, mode, st, ost)
         idx.close()
+
+
+# ---- the stand-alone kernels at every width and at the sizes where k_topk_merge's sort changes shape ----
+
+DIST_WIDTHS = [64, 128, 192, 256, 320, 384, 512, 768, 1024]  # every d_padded lm_dist_gather is compiled for (NCH = 1 .. 6, 8, 12, 16)
+
+
+@pytest.mark.parametrize("dp", DIST_WIDTHS)
+def test_dist_gather_every_width_every_pair(env, dp):
+    """Both metrics, fp32 / fp16 rows, npairs below, at and just above one workgroup's 16 pairs and over several workgroups: every pair
+    carries orc_dist's bits, repeated (qidx, id) pairs carry identical bits, and nothing is written past out[npairs]."""
+    from leann_amd import _lib
+    from oracle import oracle as orc
+    from tests.gpu_abi_util import FILL_F32_BITS, dist_gather
+
+    rng = np.random.default_rng(1700 + dp)
+    n, nq = 200, 9
+    x = rng.standard_normal((n, dp)).astype(np.float32)
+    q = rng.standard_normal((nq, dp)).astype(np.float32)
+    x[:, dp - 3 :] = 0.0  # zero padding, as the table layout has it
+    q[:, dp - 3 :] = 0.0
+    for dtype in (np.float32, np.float16):
+        xt = x.astype(dtype)
+        xf = xt.astype(np.float32)
+        for metric in (0, 1):
+            for npairs in (1, 15, 16, 17, 300):
+                ids = rng.integers(0, n, npairs).astype(np.int32)
+                qidx = rng.integers(0, nq, npairs).astype(np.int32)
+                if npairs >= 15:  # repeated pairs, in different 16-lane groups and workgroups
+                    ids[npairs - 1], qidx[npairs - 1] = ids[0], qidx[0]
+                    ids[7], qidx[7] = ids[2], qidx[2]
+                rc, got, guard = dist_gather(xt, dp, metric, q, qidx, ids)
+                assert rc == _lib.LM_OK, (dp, dtype, metric, npairs)
+                exp = np.array([orc.dist(xf[ids[p]], q[qidx[p]], metric) for p in range(npairs)], dtype=np.float32)
+                assert np.array_equal(got.view(np.uint32), exp.view(np.uint32)), (dp, dtype, metric, npairs)
+                assert (guard == FILL_F32_BITS).all(), (dp, dtype, metric, npairs)
+                if npairs >= 15:
+                    assert got.view(np.uint32)[npairs - 1] == got.view(np.uint32)[0] and got.view(np.uint32)[7] == got.view(np.uint32)[2]
+
+
+@pytest.mark.parametrize("dp", [448, 48])
+def test_dist_gather_rejects_unsupported_widths(env, dp):
+    from leann_amd import _lib
+    from tests.gpu_abi_util import FILL_F32_BITS, dist_gather
+
+    x = np.ones((20, 448), np.float32)
+    q = np.ones((3, 448), np.float32)
+    for dtype in (np.float32, np.float16):
+        for metric in (0, 1):
+            rc, got, guard = dist_gather(x.astype(dtype), dp, metric, q, np.zeros(17, np.int32), np.arange(17, dtype=np.int32))
+            assert rc == _lib.LM_EINVAL
+            assert (got.view(np.uint32) == FILL_F32_BITS).all() and (guard == FILL_F32_BITS).all()
+
+
+# (S, B, k): one key; one shard; P2 = 32 < the workgroup's 64 lanes; P2 = 64; the existing shape (P2 = 128); P2 = 2048 with S k < P2; S k = 2048
+MERGE_SEED = 1800  # (chosen so that the inputs hold every feature test_topk_merge_inputs_hold_every_named_feature asks for)
+MERGE_SHAPES = [(1, 1, 1), (1, 5, 10), (3, 7, 10), (4, 3, 16), (8, 37, 10), (20, 2, 100), (16, 2, 128)]
+
+
+def _merge_seed(si, metric):
+    return MERGE_SEED + 10 * si + metric
+
+
+def _merge_input(S, B, k, metric, seed):
+    """Shard lists [S, B, k], each sorted best first with its empty slots (-1, the metric's fill distance) at the end.  Distances are
+    multiples of 1/4 -- equal distances across shards under different ids, exact zeros of both signs -- and, on the side that
+    is worst for the metric, infinities under valid ids; ids are drawn up to 2^62.  With B >= 2 query 0 has every slot empty; with
+    B >= 3 query 1 has fewer than k valid entries in total, one of them infinitely far; with S >= 2 the last query's shard 1 repeats
+    shard 0's list, (distance, id) pair by pair.  No NaN."""
+    rng = np.random.default_rng(seed)
+    worst = np.float32(np.inf if metric == 1 else -np.inf)
+    ids = rng.integers(0, 2**62, (S, B, k), dtype=np.int64)
+    # internal distance / 0.25: 2 S + 2 values from -1 up, so about k / 2 entries of a query are below zero and k / 2 are zeros -- the zeros reach the output
+    r = rng.integers(-1, 2 * S + 1, (S, B, k))
+    r[:, 3::4] = rng.integers(-8, 9, (S, B, k))[:, 3::4]  # every fourth query: as many negative as positive values
+    dist = (r * 0.25).astype(np.float32) * np.float32(1.0 if metric == 1 else -1.0)
+    dist[r == 0] = np.where(rng.random(int((r == 0).sum())) < 0.5, np.float32(-0.0), np.float32(0.0))
+    dist[rng.random((S, B, k)) < 0.04] = worst
+    nv = np.where(rng.random((S, B)) < 0.5, k, rng.integers(0, k + 1, (S, B)))
+    if B >= 2:
+        nv[:, 0] = 0
+    if B >= 3:
+        nv[:, 1] = rng.integers(0, (k - 1) // S + 1, S)
+        nv[0, 1] = max(1, (k - 1) // S) if k > 1 else 0
+    internal = dist if metric == 1 else -dist
+    o = np.argsort(internal, axis=2, kind="stable")
+    dist = np.take_along_axis(dist, o, 2)
+    if B >= 3 and nv[0, 1]:
+        dist[0, 1, nv[0, 1] - 1] = worst  # the last valid entry of shard 0: the list stays sorted
+    if S >= 2:
+        ids[1, B - 1], dist[1, B - 1], nv[1, B - 1] = ids[0, B - 1], dist[0, B - 1], nv[0, B - 1]
+    empty = np.arange(k)[None, None, :] >= nv[:, :, None]
+    ids[empty] = -1
+    dist[empty] = worst
+    return np.ascontiguousarray(ids), np.ascontiguousarray(dist)
+
+
+def _merge_features(ids, dist, metric):
+    """Which of the named data features these shard lists hold (a set of names), read from the inputs alone."""
+    S, B, k = ids.shape
+    worst = np.inf if metric == 1 else -np.inf
+    have = set()
+    valid = ids >= 0
+    if (valid & (ids > 2**32)).any():
+        have.add("ids above 2^32")
+    if (valid & (dist == 0) & np.signbit(dist)).any() and (valid & (dist == 0) & ~np.signbit(dist)).any():
+        have.add("zeros of both signs")
+    if (valid & (dist == worst)).any():
+        have.add("valid entry infinitely far")
+    for b in range(B):
+        nvalid = int(valid[:, b].sum())
+        if nvalid == 0:
+            have.add("query with every slot empty")
+        elif nvalid < k:
+            have.add("query with fewer than k valid entries")
+            if (valid[:, b] & (dist[:, b] == worst)).any():
+                have.add("infinitely far entry ahead of empty output slots")
+        sh = np.repeat(np.arange(S), k)[valid[:, b].reshape(-1)]
+        dd, ii = dist[:, b][valid[:, b]], ids[:, b][valid[:, b]]
+        other = sh[:, None] != sh[None, :]
+        same_d = dd[:, None] == dd[None, :]
+        same_i = ii[:, None] == ii[None, :]
+        if (other & same_d & ~same_i).any():
+            have.add("equal distances across shards, different ids")
+        if (other & same_d & same_i).any():
+            have.add("the same (distance, id) in two shards")
+    return have
+
+
+MERGE_FEATURES = {"ids above 2^32", "zeros of both signs", "valid entry infinitely far", "query with every slot empty", "query with fewer than k valid entries",
+                  "infinitely far entry ahead of empty output slots", "equal distances across shards, different ids", "the same (distance, id) in two shards"}
+
+
+def merge_features_present():
+    """For each metric: the features held by at least one of MERGE_SHAPES' inputs."""
+    out = {}
+    for metric in (0, 1):
+        out[metric] = set()
+        for si, (S, B, k) in enumerate(MERGE_SHAPES):
+            out[metric] |= _merge_features(*_merge_input(S, B, k, metric, _merge_seed(si, metric)), metric)
+    return out
+
+
+def test_topk_merge_inputs_hold_every_named_feature(env):
+    from oracle import oracle as orc
+
+    have = merge_features_present()
+    assert have[0] == MERGE_FEATURES and have[1] == MERGE_FEATURES, (MERGE_FEATURES - have[0], MERGE_FEATURES - have[1])
+    # and where the sort needs them: signed zeros, ties across shards and repeated pairs at a P2 below, at and above the 64 lanes
+    for S, B, k in ((3, 7, 10), (4, 3, 16), (20, 2, 100)):
+        for metric in (0, 1):
+            f = _merge_features(*_merge_input(S, B, k, metric, _merge_seed(MERGE_SHAPES.index((S, B, k)), metric)), metric)
+            assert {"zeros of both signs", "equal distances across shards, different ids", "the same (distance, id) in two shards", "query with every slot empty"} <= f, (S, B, k, metric, f)
+            # the oracle's OUTPUT holds zeros of both signs: a kernel that rebuilds the distance from its sort key cannot pass
+            _, ed = orc.merge_topk(*_merge_input(S, B, k, metric, _merge_seed(MERGE_SHAPES.index((S, B, k)), metric)), metric)
+            assert ((ed == 0) & np.signbit(ed)).any() and ((ed == 0) & ~np.signbit(ed)).any(), (S, B, k, metric)
+
+
+@pytest.mark.parametrize("S,B,k", MERGE_SHAPES)
+def test_topk_merge_ids_and_distance_bits(env, S, B, k):
+    """lm_topk_merge against orc_merge_topk, both metrics: ids exactly and distances as bits -- a zero comes back with the sign it went in
+    with, an infinitely far valid entry with its id ahead of the -1 slots, an empty query as -1 and the metric's fill --; every output
+    element is written and nothing after them."""
+    from leann_amd import _lib
+    from oracle import oracle as orc
+    from tests.gpu_abi_util import FILL_F32_BITS, FILL_I64, topk_merge
+
+    for metric in (0, 1):
+        ids, dist = _merge_input(S, B, k, metric, _merge_seed(MERGE_SHAPES.index((S, B, k)), metric))
+        assert not np.isnan(dist).any()
+        ei, ed = orc.merge_topk(ids, dist, metric)
+        fill = np.float32(np.inf if metric == 1 else -np.inf)
+        # the contract, on the oracle's output: empty slots are -1 with the fill, after every valid entry -- the infinitely far ones included
+        nvalid = np.minimum((ids >= 0).sum((0, 2)), k)
+        assert all((ei[b, : nvalid[b]] >= 0).all() and (ei[b, nvalid[b] :] == -1).all() and (ed[b, nvalid[b] :].view(np.uint32) == fill.view(np.uint32)).all() for b in range(B))
+        rc, gi, gd, gi_guard, gd_guard = topk_merge(ids, dist, metric)
+        assert rc == _lib.LM_OK, (S, B, k, metric)
+        assert (gi_guard == FILL_I64).all() and (gd_guard == FILL_F32_BITS).all()
+        assert np.array_equal(gi, ei), (S, B, k, metric, np.argwhere(gi != ei)[:5])
+        bad = np.argwhere(gd.view(np.uint32) != ed.view(np.uint32))
+        assert bad.shape[0] == 0, (S, B, k, metric, bad[:5], gd[tuple(bad[0])], ed[tuple(bad[0])])
+        rc, gi2, gd2, _, _ = topk_merge(ids, dist, metric)
+        assert rc == _lib.LM_OK and gi2.tobytes() == gi.tobytes() and gd2.tobytes() == gd.tobytes()
+
+
+def test_topk_merge_envelope(env):
+    """S k = 2176 > 2048 is refused with the outputs untouched; B = 0 is fine and writes nothing."""
+    from leann_amd import _lib
+    from tests.gpu_abi_util import FILL_F32_BITS, FILL_I64, topk_merge
+
+    for metric in (0, 1):
+        ids, dist = _merge_input(17, 1, 128, metric, 1900 + metric)
+        rc, gi, gd, gi_guard, gd_guard = topk_merge(ids, dist, metric)
+        assert rc == _lib.LM_EINVAL and "2048" in _lib.last_error()
+        assert (gi == FILL_I64).all() and (gd.view(np.uint32) == FILL_F32_BITS).all() and (gi_guard == FILL_I64).all() and (gd_guard == FILL_F32_BITS).all()
+        rc, gi, gd, gi_guard, gd_guard = topk_merge(np.zeros((4, 0, 10), np.int64), np.zeros((4, 0, 10), np.float32), metric)
+        assert rc == _lib.LM_OK and gi.shape == (0, 10)
+        assert (gi_guard == FILL_I64).all() and (gd_guard == FILL_F32_BITS).all()
