@@ -266,6 +266,38 @@ int lm_topk_merge(const int64_t *d_in_ids, const float *d_in_dist, int32_t S, in
 int lm_select_neighbors(const void *d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric,
                         const int32_t *d_cand, const float *d_dist, int64_t n, int32_t K, int32_t m, float alpha,
                         uint8_t *d_keep, void *stream);
+/* Exact top-k over a stored-embedding table = oracle/lm_oracle.c:orc_bruteforce_topk (the paper's IndexFlatIP baseline) plus an allow-list.  The
+ * reference has no such path: leann/api.py:785-790 applies metadata_filters AFTER the graph search, so a filtered query returns fewer than top_k
+ * hits; here the filter is part of the scan and the result is the best k of the allowed rows.  (csrc/lm_exact_impl.h)
+ *   d_table [ntable][d_padded]  fp32 or fp16 rows, zero padded (lm_dist_gather's layout);
+ *   d_q     [nq][d_padded]      fp32, zero padded;
+ *   d_allow                     NULL = every row, else ceil(ntable / 32) words: row i takes part iff bit i & 31 of d_allow[i >> 5] is set; bits at
+ *                               positions >= ntable of the last word are ignored, whatever their value;
+ *   d_distances / d_labels [nq][k]   out: squared L2 ascending, or +ip descending; slots beyond the number of participating rows get label -1
+ *                               and distance +inf (L2) / -inf (ip).
+ * The contract is the arithmetic.  Every (query, row) distance is the canonical reduction orc_dist (16 lanes per row, four fmaf chains per lane,
+ * xor-8/4/2/1 butterfly; internal distance = squared L2 or -ip), no matrix cores, no other summation order.  Ranking is by the key
+ * (internal distance, id) ascending: NaN ranks as +inf, -0 as +0, ties go to the lower id.  Returned distances are what the key decodes to
+ * (L2: the key's distance; ip: its negation, so an inner product of exactly 0 comes back as -0.0, as from the oracle).  The result depends on the
+ * input bits only: however the rows are cut into slices, labels and distance bits are the same.
+ * Slicing (a pure function of ntable and nq, never of the device): nqt = max(1, ceil(nq / 8)) query tiles;
+ * s0 = clamp(ceil(ntable / 1024), 1, max(1, 512 / nqt)); rows per slice = max(32, ceil(ntable / s0) rounded up to a multiple of 32);
+ * S = max(1, ceil(ntable / rows)) slices.  One query: ntable <= 1024 is one slice, 1025..2048 two, 20000 twenty (the last of 544 rows).
+ * The workspace holds the S partial lists per query: lm_exact_search_workspace_bytes = S * nq * k * 8.
+ * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width the search kernels do not cover, unknown dtype or metric, k < 1 or
+ * k > LM_EXACT_MAX_K, negative nq / ntable, ntable > INT32_MAX, a NULL buffer where one is needed, workspace_bytes below
+ * lm_exact_search_workspace_bytes(ntable, nq, k).  nq == 0: LM_OK.  ntable == 0: every slot gets the empty values. */
+#define LM_EXACT_MAX_K 256
+size_t lm_exact_search_workspace_bytes(int64_t ntable, int64_t nq, int32_t k);
+int lm_exact_search(const void *d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric, const float *d_q, int64_t nq,
+                    int32_t k, const uint32_t *d_allow, float *d_distances, int64_t *d_labels, void *d_workspace, size_t workspace_bytes,
+                    void *stream);
+/* The same on the index's attached table (library-owned or borrowed), on the index's stream, with a workspace the index owns (apart from the
+ * graph search's).  Queries are [n][d], as for lm_index_search*; `allow` of the host form is a HOST array (or NULL), uploaded per call.
+ * LM_ESTATE without an attached table. */
+int lm_index_search_exact(lm_index *idx, int64_t n, const float *x, int32_t k, const uint32_t *allow, float *distances, int64_t *labels);
+int lm_index_search_exact_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const uint32_t *d_allow, float *d_distances,
+                                 int64_t *d_labels);
 /* Index build time: the product quantiser that lm_pq_attach / lm_pq_attach_chunked take, made by the library -- nearest-centroid
  * assignment (lm_pq_encode) and Lloyd iterations over a sample (lm_pq_train); the role of DiskANN's generate_pq_pivots /
  * generate_pq_data_from_pivots behind diskann_backend.py:105-111 (leann_amd/pq.py holds the torch forms).

@@ -376,8 +376,15 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
                pruning_strategy: Literal["global", "local", "proportional"] = "global", batch_size: int = 0,
                **kwargs) -> dict[str, Any]:
         """Same contract as HNSWSearcher.search (hnsw_backend.py:153-253):
-        returns {"labels": list[list[str]] (B x k), "distances": np.ndarray (B, k) float32}."""
-        if not recompute_embeddings and self.is_pruned:
+        returns {"labels": list[list[str]] (B x k), "distances": np.ndarray (B, k) float32}.
+        ``exact=True`` (keyword, default off; needs ``recompute_embeddings=False`` and stored embeddings): the exact top-k of the stored table
+        (lm_index_search_exact) instead of the graph search; ``allowed_ids`` (keyword, with ``exact=True`` only: an iterable of integer ids or a
+        bool mask over the index) restricts it to those rows -- the best ``top_k`` of the ALLOWED rows come back, where the reference filters after
+        its search (leann/api.py:785-790) and returns fewer.  Slots without a row are label "-1", as from the graph search."""
+        exact, allowed_ids = bool(kwargs.get("exact", False)), kwargs.get("allowed_ids")
+        if allowed_ids is not None and not exact:
+            raise ValueError("allowed_ids needs exact=True: the graph kernels take no filter")
+        if (not recompute_embeddings or exact) and (self.is_pruned or (exact and recompute_embeddings)):
             raise RuntimeError(
                 "Recompute is required for pruned/compact HNSW index. "
                 "Re-run search with --recompute, or rebuild with --no-recompute and --no-compact.")
@@ -389,6 +396,11 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
         if self.distance_metric == "cosine":
             query = normalize_l2(query)
         idx = self._ensure_index_loaded()
+        if exact:
+            t0 = time.time()
+            distances, labels = idx.search_exact(np.ascontiguousarray(query), int(top_k), allowed=allowed_ids)
+            logger.info(f"  Search time in Mi355xSearcher.search() backend (exact): {time.time() - t0} seconds")
+            return {"labels": [[str(int(l)) for l in row] for row in labels], "distances": distances}
         if recompute_embeddings and self._provider is None:
             self._ensure_server_running(str(self.index_dir / f"{self.index_path.name}.meta.json"), zmq_port)
         # hnsw_backend.py:209-217: OpenAI cosine models disable the relative distance check

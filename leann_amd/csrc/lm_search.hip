@@ -12,6 +12,7 @@
 //   k_search_table persistent stored-embedding search: a query's whole traversal in one workgroup, one launch/batch
 //   lm_pq_impl.h  DiskANN-style path: k_pq_traverse (persistent PQ-ADC traversal), k_pq_rerank
 //   lm_select_impl.h  index build time: k_select_neighbors (HNSW select-neighbours heuristic, 16 lanes per row)
+//   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
 #include <algorithm>
@@ -99,6 +100,10 @@ struct lm_index {
     std::vector<void*> ws_allocs;
     float* d_qpad = nullptr;
     int64_t qpad_cap = 0;
+    // lm_index_search_exact*: partial top-k lists and the uploaded allow-list, grown on demand, apart from the graph search's workspace
+    void* d_exact_ws = nullptr;
+    uint32_t* d_exact_allow = nullptr;
+    size_t exact_ws_bytes = 0, exact_allow_bytes = 0;
     unsigned long long* h_counters = nullptr;  // pinned
     // stats / profiling
     lm_search_stats stats{};
@@ -768,6 +773,8 @@ void lm_index_free(lm_index* ix) {
     if (ix->d_tstamp) (void)hipFree(ix->d_tstamp);
     if (ix->d_table && ix->table_owned) (void)hipFree(ix->d_table);
     if (ix->d_qpad) (void)hipFree(ix->d_qpad);
+    if (ix->d_exact_ws) (void)hipFree(ix->d_exact_ws);
+    if (ix->d_exact_allow) (void)hipFree(ix->d_exact_allow);
     if (ix->h_counters) (void)hipHostFree(ix->h_counters);
     (void)drain_events(ix, ix->ev_update);
     (void)drain_events(ix, ix->ev_expand);
@@ -1057,4 +1064,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_pq_impl.h"
 #include "lm_select_impl.h"
 #include "lm_pq_build_impl.h"
+#include "lm_exact_impl.h"
 

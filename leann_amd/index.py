@@ -19,6 +19,26 @@ def _np_ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def allow_bitmap(allowed, ntotal: int) -> np.ndarray:
+    """The allow-list of lm_exact_search as uint32 words [ceil(ntotal / 32)]: row i takes part iff bit i & 31 of word i >> 5 is set.
+    ``allowed``: a bool mask [ntotal] or an array of row ids (duplicates are fine; an id outside [0, ntotal) is an error)."""
+    a = np.asarray(allowed)
+    if a.dtype == np.bool_:
+        if a.shape != (ntotal,):
+            raise ValueError(f"a bool mask must have shape ({ntotal},)")
+        mask = a
+    else:
+        ids = a.astype(np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= ntotal):
+            raise ValueError(f"allowed ids must lie in [0, {ntotal})")
+        mask = np.zeros(ntotal, np.bool_)
+        mask[ids] = True
+    nw = (ntotal + 31) // 32
+    bits = np.zeros(nw * 32, np.uint8)
+    bits[:ntotal] = mask
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u4")).astype(np.uint32, copy=False)
+
+
 class Mi355xIndex:
     """Owns one ``lm_index``.  Create with :meth:`from_csr` or :meth:`read`."""
 
@@ -195,6 +215,43 @@ class Mi355xIndex:
         rc = self._lib.lm_index_search_device(self._h, n, C.c_void_p(queries.data_ptr()), k, C.c_void_p(dist.data_ptr()),
                                               C.c_void_p(labels.data_ptr()), C.byref(params))
         self._raise_provider(rc, "lm_index_search_device")
+        return dist, labels
+
+    # ---- exact search over the attached table -----------------------------------------------------
+    def search_exact(self, queries: np.ndarray, k: int, allowed=None):
+        """Exact top-k of the attached table (lm_index_search_exact == oracle bruteforce_topk + allow-list): (distances, labels) numpy,
+        slots without a row -1 / +-inf.  ``allowed``: None, a bool mask [ntotal] or an array of row ids."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.info.d:
+            raise ValueError(f"query must be (B, {self.info.d}) float32")
+        n = q.shape[0]
+        dist = np.empty((n, k), dtype=np.float32)
+        labels = np.empty((n, k), dtype=np.int64)
+        words = None if allowed is None else allow_bitmap(allowed, int(self.info.ntotal))
+        check(self._lib.lm_index_search_exact(self._h, n, _np_ptr(q), k, None if words is None else _np_ptr(words), _np_ptr(dist), _np_ptr(labels)),
+              "lm_index_search_exact")
+        return dist, labels
+
+    def search_exact_device(self, queries, k: int, allowed=None):
+        """The same with ``queries`` a CUDA/HIP torch tensor (B, D) f32; returns torch tensors.  ``allowed`` as for :meth:`search_exact`, or a
+        device int32 tensor that already holds the bitmap words."""
+        import torch
+
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        n = queries.shape[0]
+        dist = torch.empty((n, k), dtype=torch.float32, device=queries.device)
+        labels = torch.empty((n, k), dtype=torch.int64, device=queries.device)
+        words = None
+        if allowed is not None:
+            if isinstance(allowed, torch.Tensor) and allowed.is_cuda and allowed.dtype == torch.int32:
+                words = allowed.contiguous()
+                if words.numel() != (int(self.info.ntotal) + 31) // 32:
+                    raise ValueError("a device bitmap must hold ceil(ntotal / 32) int32 words")
+            else:
+                host = allowed.cpu().numpy() if isinstance(allowed, torch.Tensor) else allowed
+                words = torch.from_numpy(allow_bitmap(host, int(self.info.ntotal)).view(np.int32)).to(queries.device)
+        check(self._lib.lm_index_search_exact_device(self._h, n, C.c_void_p(queries.data_ptr()), k, None if words is None else C.c_void_p(words.data_ptr()),
+                                                     C.c_void_p(dist.data_ptr()), C.c_void_p(labels.data_ptr())), "lm_index_search_exact_device")
         return dist, labels
 
     # ---- DiskANN-style path -----------------------------------------------------------------
