@@ -243,6 +243,10 @@ __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev
             ws.pool[(size_t)q * ws.ef + nexp + tid] = make_key(0.0f, s_pop[tid]);
         nexp += np;
         const uint32_t totalc = s_off[np];
+        if (totalc == 0) {  // no pop has a neighbour: nothing below passes a barrier, and wave 0 must not select the next pops (s_npop, s_off) before every wave has read this hop's
+            __syncthreads();
+            continue;
+        }
         // ---- flattened expansion over the workgroup, visited test-and-set, ordered compaction ----
         // (round 6) EP passes of the workgroup in flight at a time: their neighbour ids are requested together (clamped indices: unconditional loads), then their
         // test-and-sets (a lane past the end ORs a zero into a word of its own), then the ordered compactions -- one global round trip per EP * NTH
