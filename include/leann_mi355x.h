@@ -298,6 +298,50 @@ int lm_exact_search(const void *d_table, int32_t dtype, int64_t ntable, int32_t 
 int lm_index_search_exact(lm_index *idx, int64_t n, const float *x, int32_t k, const uint32_t *allow, float *distances, int64_t *labels);
 int lm_index_search_exact_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const uint32_t *d_allow, float *d_distances,
                                  int64_t *d_labels);
+/* Flat PQ scan: the L best rows of an N x m code array by ADC distance, with an allow-list -- the filtered search of an index that stores no
+ * embeddings (it keeps its PQ codes and the recompute provider).  No graph is walked, so a filter cannot disconnect it, and the allow-list is
+ * part of the scan: rejected rows are never loaded.  (csrc/lm_pq_flat_impl.h)
+ *   d_codes [ntotal][m]          code bytes (lm_pq_attach's layout), 4-byte aligned (the rows are read as dwords; 16-byte alignment lets
+ *                                the kernel fetch a row as 16-byte pieces at m = 16, 32, 48, 64, 96, 128);
+ *   chunk_offsets                HOST array of m + 1 offsets by the rules of lm_pq_attach_chunked (chunk_offsets[m] <= d), NULL = uniform d / m;
+ *   d_codebooks                  lm_pq_attach's layout: chunk j's 256 centroids x len_j floats at float offset 256 * chunk_offsets[j];
+ *   d_q [nq][ldq]                fp32 queries, ldq >= d;
+ *   d_allow                      lm_exact_search's layout and rules (NULL = every row; bits at positions >= ntotal are ignored);
+ *   d_distances / d_labels [nq][L]   out: ADC distance ascending (L2) or its negation descending (ip), decoded as k_finalize decodes a pool key;
+ *                                slots beyond the number of participating rows get label -1 and +inf (L2) / -inf (ip).
+ * The contract is the arithmetic of oracle/lm_oracle_pq.c.  Lookup table (orc_pq_lut): LUT[j][c] = the sequential fmaf sum over the chunk's
+ * dimensions of (q - centroid)^2 (L2) or of q * centroid, negated (ip); a zero-length chunk gives 0 (-0 under ip).  Distance (orc_pq_adc):
+ * adc = (p0 + p1) + (p2 + p3), p_r = the sequential fp32 sum over j = r, r + 4, ... of LUT[j][code[j]]; no other order, no contraction.
+ * Ranking is by the key (adc, id) ascending: NaN ranks as +inf, -0 as +0, ties go to the lower id.  The result depends on the input bits
+ * only: however the rows are cut into slices, labels and distance bits are the same.
+ * Slicing (a pure function of ntotal, nq, m and L, never of the device):
+ *   per_q = 1024 m + 16 L + 10240 bytes of LDS per query (its table, two lists of L keys, 1280 pending keys);
+ *   qt    = min(8, floor(161792 / per_q)) queries per tile (one at m = 96, two at m = 48, eight at m = 8 and L <= 112);
+ *   nqt   = max(1, ceil(nq / qt)) query tiles;  s0 = clamp(ceil(ntotal / 2048), 1, max(1, 512 / nqt));
+ *   rows per slice = max(32, ceil(ntotal / s0) rounded up to a multiple of 32);  S = max(1, ceil(ntotal / rows)) slices.
+ * One query: ntotal <= 2048 is one slice, 2049 .. 4096 two, 4097 three, 20000 ten (nine of 2016 rows and a last one of 1856), 1M rows 489
+ * of 2048.  The workspace holds the S partial lists per query: lm_pq_scan_workspace_bytes = S * nq * L * 8 (0 for arguments lm_pq_scan rejects).
+ * LM_EINVAL (before anything is launched): m < 1, m % 4 != 0 or m > 4096; offsets that do not start at 0, decrease or end past d; uniform
+ * layout with d % m != 0; ldq < d; L < 1 or L > LM_PQ_FLAT_MAX_L; qt == 0 (table + lists do not fit the 160 KB LDS); unknown metric; negative
+ * nq / ntotal, ntotal > INT32_MAX; d_codes not 4-byte aligned; a NULL buffer where one is needed; workspace_bytes below lm_pq_scan_workspace_bytes(ntotal, nq, m, L).
+ * nq == 0: LM_OK.  ntotal == 0: every slot gets the empty values. */
+#define LM_PQ_FLAT_MAX_L 1024
+size_t lm_pq_scan_workspace_bytes(int64_t ntotal, int64_t nq, int32_t m, int32_t L);
+int lm_pq_scan(const uint8_t *d_codes, int64_t ntotal, int32_t m, const int32_t *chunk_offsets, const float *d_codebooks, int32_t d,
+               int32_t metric, const float *d_q, int64_t nq, int32_t ldq, int32_t L, const uint32_t *d_allow, float *d_distances,
+               int64_t *d_labels, void *d_workspace, size_t workspace_bytes, void *stream);
+/* The same on the index's attached quantiser and stream, followed by the tail of lm_pq_batch_search: L = max(params->complexity, k) rows
+ * per query come out of the scan; with use_deferred_fetch and a provider they are re-ranked by exact distances of embeddings fetched in
+ * ONE provider call (the sorted unique union of the lists), else by the stored table if there is one, else -- or with skip_search_reorder --
+ * the PQ order stands; then the best k go out.  beam_width and the inert knobs are accepted and unused; recompute_neighbors != 0: LM_EINVAL.
+ * `allow` of the host form is a HOST array (or NULL), uploaded per call.  LM_EINVAL also for complexity < 1, k < 1, max(complexity, k) >
+ * LM_PQ_FLAT_MAX_L or a scan state that does not fit the LDS (lm_pq_scan's rule).  LM_ESTATE without attached codes, or when deferred fetch is
+ * asked for with neither a provider nor a table.  Every rejection comes before anything is staged or launched: the outputs stay untouched.  Stats: ndis = ADC evaluations (allowed rows x queries), nunique = rows requested from the
+ * provider, nrounds = 1, nexpand = 0.  The index owns the scan's workspace, apart from the other paths'. */
+int lm_pq_flat_search(lm_index *idx, int64_t n, const float *x, int32_t k, const lm_pq_search_params *params, const uint32_t *allow,
+                      int64_t *labels, float *distances);
+int lm_pq_flat_search_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const lm_pq_search_params *params,
+                             const uint32_t *d_allow, int64_t *d_labels, float *d_distances);
 /* Index build time: the product quantiser that lm_pq_attach / lm_pq_attach_chunked take, made by the library -- nearest-centroid
  * assignment (lm_pq_encode) and Lloyd iterations over a sample (lm_pq_train); the role of DiskANN's generate_pq_pivots /
  * generate_pq_data_from_pivots behind diskann_backend.py:105-111 (leann_amd/pq.py holds the torch forms).

@@ -378,12 +378,18 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
         """Same contract as HNSWSearcher.search (hnsw_backend.py:153-253):
         returns {"labels": list[list[str]] (B x k), "distances": np.ndarray (B, k) float32}.
         ``exact=True`` (keyword, default off; needs ``recompute_embeddings=False`` and stored embeddings): the exact top-k of the stored table
-        (lm_index_search_exact) instead of the graph search; ``allowed_ids`` (keyword, with ``exact=True`` only: an iterable of integer ids or a
-        bool mask over the index) restricts it to those rows -- the best ``top_k`` of the ALLOWED rows come back, where the reference filters after
-        its search (leann/api.py:785-790) and returns fewer.  Slots without a row are label "-1", as from the graph search."""
+        (lm_index_search_exact) instead of the graph search; ``allowed_ids`` (keyword, with ``exact=True`` or ``pq_flat=True`` only: an iterable of
+        integer ids or a bool mask over the index) restricts it to those rows -- the best ``top_k`` of the ALLOWED rows come back, where the
+        reference filters after its search (leann/api.py:785-790) and returns fewer.  Slots without a row are label "-1", as from the graph search.
+        ``pq_flat=True`` (keyword, default off; needs a product quantiser: build with ``pq_bytes=...``): the filtered search of a pruned index
+        (lm_pq_flat_search) -- a flat PQ-ADC scan of the allowed rows keeps the ``complexity`` best, which are re-ranked exactly through the
+        recompute provider in one call (``recompute_embeddings=True``) or through the stored table (``False``; refused on a pruned index)."""
         exact, allowed_ids = bool(kwargs.get("exact", False)), kwargs.get("allowed_ids")
-        if allowed_ids is not None and not exact:
-            raise ValueError("allowed_ids needs exact=True: the graph kernels take no filter")
+        pq_flat = bool(kwargs.get("pq_flat", False))
+        if allowed_ids is not None and not (exact or pq_flat):
+            raise ValueError("allowed_ids needs exact=True or pq_flat=True: the graph kernels take no filter")
+        if exact and pq_flat:
+            raise ValueError("exact=True and pq_flat=True are two different searches: choose one")
         if (not recompute_embeddings or exact) and (self.is_pruned or (exact and recompute_embeddings)):
             raise RuntimeError(
                 "Recompute is required for pruned/compact HNSW index. "
@@ -401,8 +407,12 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
             distances, labels = idx.search_exact(np.ascontiguousarray(query), int(top_k), allowed=allowed_ids)
             logger.info(f"  Search time in Mi355xSearcher.search() backend (exact): {time.time() - t0} seconds")
             return {"labels": [[str(int(l)) for l in row] for row in labels], "distances": distances}
+        if pq_flat and not getattr(self, "_has_pq", False):
+            raise RuntimeError("pq_flat=True needs a product quantiser (<stem>_pq.npz): build the index with pq_bytes=...")
         if recompute_embeddings and self._provider is None:
             self._ensure_server_running(str(self.index_dir / f"{self.index_path.name}.meta.json"), zmq_port)
+        if pq_flat:
+            return self._pq_flat_search(idx, query, top_k, complexity, recompute_embeddings, allowed_ids, kwargs)
         # hnsw_backend.py:209-217: OpenAI cosine models disable the relative distance check
         if prune_ratio and not getattr(self, "_has_pq", False):
             logger.warning("prune_ratio > 0 needs a product quantiser (<stem>_pq.npz, build with pq_bytes=...); ignoring it")
@@ -426,6 +436,19 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
         logger.info(f"  Search time in Mi355xSearcher.search() backend: {time.time() - t0} seconds")
         string_labels = [[str(int(l)) for l in row] for row in labels]
         return {"labels": string_labels, "distances": distances}
+
+    def _pq_flat_search(self, idx, query: np.ndarray, top_k: int, complexity: int, recompute_embeddings: bool, allowed_ids, kwargs) -> dict[str, Any]:
+        """search(..., pq_flat=True): ``complexity`` is the scan's L; the rerank goes through the provider (recompute) or the stored table."""
+        if recompute_embeddings:
+            import torch
+
+            idx.set_stream(torch.cuda.current_stream(self._torch_device()).cuda_stream)
+        params = idx.make_pq_params(int(complexity), 1, use_deferred_fetch=bool(recompute_embeddings),
+                                    skip_search_reorder=bool(kwargs.get("skip_search_reorder", False)))
+        t0 = time.time()
+        labels, distances = idx.pq_flat_search(np.ascontiguousarray(query), int(top_k), params, allowed=allowed_ids)
+        logger.info(f"  Search time in Mi355xSearcher.search() backend (pq_flat): {time.time() - t0} seconds")
+        return {"labels": [[str(int(l)) for l in row] for row in labels], "distances": distances}
 
     def last_stats(self) -> dict:
         return self._index.stats() if self._index is not None else {}
@@ -598,7 +621,11 @@ class Mi355xDiskannSearcher(Mi355xSearcher):
                recompute_embeddings: bool = False, pruning_strategy: Literal["global", "local", "proportional"] = "global",
                zmq_port: Optional[int] = None, batch_recompute: bool = False, dedup_node_dis: bool = False,
                **kwargs) -> dict[str, Any]:
-        """Same contract as DiskannSearcher.search (diskann_backend.py:383-471)."""
+        """Same contract as DiskannSearcher.search (diskann_backend.py:383-471).  ``pq_flat=True`` / ``allowed_ids`` (keywords, default off): the
+        flat PQ scan of the allowed rows in place of the traversal, with the same rerank (Mi355xSearcher.search)."""
+        pq_flat, allowed_ids = bool(kwargs.get("pq_flat", False)), kwargs.get("allowed_ids")
+        if allowed_ids is not None and not pq_flat:
+            raise ValueError("allowed_ids needs pq_flat=True: the traversal kernel takes no filter")
         if recompute_embeddings and zmq_port is None:
             raise ValueError("zmq_port must be provided if recompute_embeddings is True")
         if pruning_strategy == "proportional":
@@ -623,6 +650,8 @@ class Mi355xDiskannSearcher(Mi355xSearcher):
             import torch
 
             idx.set_stream(torch.cuda.current_stream(self._torch_device()).cuda_stream)
+        if pq_flat:
+            return self._pq_flat_search(idx, query, top_k, complexity, recompute_embeddings, allowed_ids, kwargs)
         # traversal always on PQ distances; recompute => one final rerank via deferred fetch (:444-450)
         params = idx.make_pq_params(int(complexity), int(beam_width), use_deferred_fetch=bool(recompute_embeddings),
                                     skip_search_reorder=bool(kwargs.get("skip_search_reorder", False)),

@@ -442,6 +442,60 @@ static int launch_rerank_nch(lm_index* ix, const UpdateArgs& a) {
     return LM_OK;
 }
 
+// The tail of a PQ search pass, shared by the traversal (pq_search_pass) and the flat scan (lm_pq_flat_impl.h): ws.pool / ws.npool hold every query's
+// candidates (at most nrank <= ws.ef of them), ws.counters the pass' totals.  rerank: their exact distances -- embeddings fetched ONCE through the
+// provider (use_deferred_fetch), else the stored table -- replace the PQ ones and each list is sorted again; then the best k go out and the totals
+// are added to the stats.
+static int pq_rerank_tail(lm_index* ix, int32_t B, const float* d_q, int32_t k, const lm_pq_search_params& prm, bool rerank, int32_t nrank,
+                          float* d_dist, int64_t* d_labels) {
+    WsDev& ws = ix->ws;
+    hipStream_t st = ix->stream;
+    int rc = LM_OK;
+    unsigned long long* hc = ix->h_counters;
+    if (rerank) {
+        UpdateArgs ua{};
+        ua.Q = d_q;
+        ua.P2 = next_pow2(nrank);
+        if ((size_t)ua.P2 * 8 > 64 * 1024) LM_FAIL(LM_EINVAL, "complexity too large for the rerank kernel (<= 8192 candidates per query)");
+        if (prm.use_deferred_fetch && ix->provider) {
+            // ONE deferred fetch for the union of all candidate lists
+            const int ntiles = (int)((ws.nw + UNIQ_TILE - 1) / UNIQ_TILE);
+            hipLaunchKernelGGL(k_pq_mark, dim3((unsigned)(((int64_t)B * ws.ef + 255) / 256)), dim3(256), 0, st, ws);
+            hipLaunchKernelGGL(k_uniq_count, dim3(ntiles), dim3(256), 0, st, ws);
+            hipLaunchKernelGGL(k_uniq_emit, dim3(ntiles), dim3(256), 0, st, ws, ntiles);
+            LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+            LM_HIP(hipStreamSynchronize(st));
+            int32_t nu = (int32_t)hc[C_NUNIQ];
+            void* d_e = nullptr;
+            ix->stats.nunique += nu;
+            if (nu > 0) {
+                EvScope es(ix, &ix->ev_provider);
+                int prc = ix->provider(ix->provider_user, ws.uniq, nu, &d_e, (void*)st);
+                if (prc != 0 || !d_e) LM_FAIL(LM_EPROVIDER, "embedding provider failed (rc=" + std::to_string(prc) + ")");
+            }
+            ua.E = d_e;
+            ua.by_rank = 1;
+            rc = ix->metric == LM_METRIC_L2 ? launch_rerank_nch<true, false>(ix, ua) : launch_rerank_nch<false, false>(ix, ua);
+        } else {
+            ua.E = ix->d_table;
+            ua.by_rank = 0;
+            const bool f16 = ix->table_dtype == LM_DTYPE_F16, l2 = ix->metric == LM_METRIC_L2;
+            rc = l2 ? (f16 ? launch_rerank_nch<true, true>(ix, ua) : launch_rerank_nch<true, false>(ix, ua))
+                    : (f16 ? launch_rerank_nch<false, true>(ix, ua) : launch_rerank_nch<false, false>(ix, ua));
+        }
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_finalize, dim3((B * k + 255) / 256), dim3(256), 0, st, ws, k, ix->metric, d_labels, d_dist);
+    LM_HIP(hipGetLastError());
+    LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    LM_HIP(hipStreamSynchronize(st));
+    ix->stats.ndis += (int64_t)hc[C_NDIS];
+    ix->stats.nexpand += (int64_t)hc[C_NEXPAND];
+    ix->stats.nrounds = std::max<int64_t>(ix->stats.nrounds, (int64_t)hc[C_ROUNDS]);
+    ix->pq_overflow += (int64_t)hc[C_PQ_OVERFLOW];
+    return LM_OK;
+}
+
 static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, const lm_pq_search_params& prm,
                           float* d_dist, int64_t* d_labels) {
     const int32_t L = std::max(prm.complexity, k);
@@ -494,49 +548,7 @@ static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, 
     LM_HIP(hipGetLastError());
     ix->stats.update_launches++;
     hipLaunchKernelGGL(k_pq_stats, dim3(1), dim3(256), 0, st, ws, pa);
-    unsigned long long* hc = ix->h_counters;
-    if (rerank) {
-        UpdateArgs ua{};
-        ua.Q = d_q;
-        ua.P2 = next_pow2(exp_cap ? exp_cap : L);
-        if ((size_t)ua.P2 * 8 > 64 * 1024) LM_FAIL(LM_EINVAL, "complexity too large for the rerank kernel (<= 8192 candidates per query)");
-        if (prm.use_deferred_fetch && ix->provider) {
-            // ONE deferred fetch for the union of all candidate lists
-            const int ntiles = (int)((ws.nw + UNIQ_TILE - 1) / UNIQ_TILE);
-            hipLaunchKernelGGL(k_pq_mark, dim3((unsigned)(((int64_t)B * ws.ef + 255) / 256)), dim3(256), 0, st, ws);
-            hipLaunchKernelGGL(k_uniq_count, dim3(ntiles), dim3(256), 0, st, ws);
-            hipLaunchKernelGGL(k_uniq_emit, dim3(ntiles), dim3(256), 0, st, ws, ntiles);
-            LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            LM_HIP(hipStreamSynchronize(st));
-            int32_t nu = (int32_t)hc[C_NUNIQ];
-            void* d_e = nullptr;
-            ix->stats.nunique += nu;
-            if (nu > 0) {
-                EvScope es(ix, &ix->ev_provider);
-                int prc = ix->provider(ix->provider_user, ws.uniq, nu, &d_e, (void*)st);
-                if (prc != 0 || !d_e) LM_FAIL(LM_EPROVIDER, "embedding provider failed (rc=" + std::to_string(prc) + ")");
-            }
-            ua.E = d_e;
-            ua.by_rank = 1;
-            rc = ix->metric == LM_METRIC_L2 ? launch_rerank_nch<true, false>(ix, ua) : launch_rerank_nch<false, false>(ix, ua);
-        } else {
-            ua.E = ix->d_table;
-            ua.by_rank = 0;
-            const bool f16 = ix->table_dtype == LM_DTYPE_F16, l2 = ix->metric == LM_METRIC_L2;
-            rc = l2 ? (f16 ? launch_rerank_nch<true, true>(ix, ua) : launch_rerank_nch<true, false>(ix, ua))
-                    : (f16 ? launch_rerank_nch<false, true>(ix, ua) : launch_rerank_nch<false, false>(ix, ua));
-        }
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_finalize, dim3((B * k + 255) / 256), dim3(256), 0, st, ws, k, ix->metric, d_labels, d_dist);
-    LM_HIP(hipGetLastError());
-    LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    LM_HIP(hipStreamSynchronize(st));
-    ix->stats.ndis += (int64_t)hc[C_NDIS];
-    ix->stats.nexpand += (int64_t)hc[C_NEXPAND];
-    ix->stats.nrounds = std::max<int64_t>(ix->stats.nrounds, (int64_t)hc[C_ROUNDS]);
-    ix->pq_overflow += (int64_t)hc[C_PQ_OVERFLOW];
-    return LM_OK;
+    return pq_rerank_tail(ix, B, d_q, k, prm, rerank, exp_cap ? exp_cap : L, d_dist, d_labels);
 }
 
 extern "C" {
@@ -564,6 +576,7 @@ int lm_pq_attach_chunked(lm_index* ix, int32_t m, const int32_t* chunk_offsets, 
     LM_HIP(hipMemcpy(ix->d_pq_codes, codes, code_bytes, hipMemcpyHostToDevice));
     LM_HIP(hipMemcpy(ix->d_pq_chunk_off, chunk_offsets, (size_t)(m + 1) * 4, hipMemcpyHostToDevice));
     ix->pq_m = m;
+    ix->h_pq_chunk_off.assign(chunk_offsets, chunk_offsets + m + 1);  // the flat scan takes them as a kernel argument
     return LM_OK;
 }
 

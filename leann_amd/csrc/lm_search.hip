@@ -13,6 +13,7 @@
 //   lm_pq_impl.h  DiskANN-style path: k_pq_traverse (persistent PQ-ADC traversal), k_pq_rerank
 //   lm_select_impl.h  index build time: k_select_neighbors (HNSW select-neighbours heuristic, 16 lanes per row)
 //   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
+//   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
 #include <algorithm>
@@ -104,6 +105,11 @@ struct lm_index {
     void* d_exact_ws = nullptr;
     uint32_t* d_exact_allow = nullptr;
     size_t exact_ws_bytes = 0, exact_allow_bytes = 0;
+    // lm_pq_flat_search*: the scan's partial lists and the uploaded allow-list, grown on demand, apart from the other paths' workspaces
+    void* d_pqflat_ws = nullptr;
+    uint32_t* d_pqflat_allow = nullptr;
+    size_t pqflat_ws_bytes = 0, pqflat_allow_bytes = 0;
+    std::vector<int32_t> h_pq_chunk_off;  // host copy of d_pq_chunk_off (m + 1)
     unsigned long long* h_counters = nullptr;  // pinned
     // stats / profiling
     lm_search_stats stats{};
@@ -775,6 +781,8 @@ void lm_index_free(lm_index* ix) {
     if (ix->d_qpad) (void)hipFree(ix->d_qpad);
     if (ix->d_exact_ws) (void)hipFree(ix->d_exact_ws);
     if (ix->d_exact_allow) (void)hipFree(ix->d_exact_allow);
+    if (ix->d_pqflat_ws) (void)hipFree(ix->d_pqflat_ws);
+    if (ix->d_pqflat_allow) (void)hipFree(ix->d_pqflat_allow);
     if (ix->h_counters) (void)hipHostFree(ix->h_counters);
     (void)drain_events(ix, ix->ev_update);
     (void)drain_events(ix, ix->ev_expand);
@@ -1065,4 +1073,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_select_impl.h"
 #include "lm_pq_build_impl.h"
 #include "lm_exact_impl.h"
+#include "lm_pq_flat_impl.h"
 

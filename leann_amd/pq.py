@@ -153,6 +153,53 @@ def train_pq_kernel(x: torch.Tensor, m: int, iters: int = 12, sample: int = 1310
     return lloyd_kernel(xs, cb, iters)
 
 
+@torch.no_grad()
+def pq_scan_kernel(codes: torch.Tensor, codebooks: torch.Tensor, queries: torch.Tensor, L: int, metric: str = "mips", chunk_offsets=None,
+                   allowed=None):
+    """The L best rows of ``codes`` [N, m] uint8 by PQ-ADC distance on the library's kernels (lm_pq_scan) -> (distances [nq, L] float32, labels
+    [nq, L] int64) on the codes' device: ADC distance ascending (``"l2"``) or its negation descending (``"mips"``), slots without a row -1 / +-inf.
+    ``codebooks`` as for encode_pq_kernel; ``queries`` [nq, d] fp32 (a column slice of wider rows passes its row stride on); ``allowed``: None, a
+    bool mask [N] / an array of row ids, or a device int32 tensor that already holds the bitmap words."""
+    from . import _lib
+    from .index import allow_bitmap
+
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise ValueError("codes must be [N, m] uint8")
+    codes = codes.contiguous()
+    n, m = int(codes.shape[0]), int(codes.shape[1])
+    q = queries.to(device=codes.device, dtype=torch.float32)
+    if q.dim() != 2:
+        raise ValueError("queries must be [nq, d]")
+    if q.shape[0] <= 1 or q.shape[1] == 0 or q.stride(1) != 1 or q.stride(0) < q.shape[1]:
+        q = q.contiguous()
+    nq, d = int(q.shape[0]), int(q.shape[1])
+    ldq = int(q.stride(0)) if nq > 1 and d > 0 else d
+    off, off_p = _kernel_chunks(chunk_offsets)
+    cb = codebooks.to(device=codes.device, dtype=torch.float32).contiguous()
+    if off is None and (cb.dim() != 3 or cb.shape[0] != m or cb.shape[1] != 256 or m * cb.shape[2] != d):
+        raise ValueError("codebooks must be [m, 256, d/m]")
+    if off is not None and (off.shape[0] != m + 1 or cb.numel() != 256 * max(int(off[-1]), 0)):
+        raise ValueError("chunked codebooks must hold 256 * chunk_offsets[m] floats and chunk_offsets m + 1 entries")
+    words = None
+    if allowed is not None:
+        if isinstance(allowed, torch.Tensor) and allowed.dtype == torch.int32 and allowed.device == codes.device and allowed.numel() == (n + 31) // 32:
+            words = allowed.contiguous()
+        else:
+            host = allowed.cpu().numpy() if isinstance(allowed, torch.Tensor) else allowed
+            words = torch.from_numpy(allow_bitmap(host, n).view(np.int32)).to(codes.device)
+    lib = _lib.load()
+    nbytes = int(lib.lm_pq_scan_workspace_bytes(n, nq, m, int(L)))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=codes.device)
+    dist = torch.empty((nq, max(int(L), 0)), dtype=torch.float32, device=codes.device)
+    labels = torch.empty((nq, max(int(L), 0)), dtype=torch.int64, device=codes.device)
+    stream = torch.cuda.current_stream(codes.device).cuda_stream if codes.is_cuda else None
+    rc = lib.lm_pq_scan(codes.data_ptr(), n, m, off_p, cb.data_ptr(), d, _lib.METRIC_L2 if metric == "l2" else _lib.METRIC_INNER_PRODUCT, q.data_ptr(),
+                        nq, ldq, int(L), None if words is None or words.numel() == 0 else words.data_ptr(), dist.data_ptr(), labels.data_ptr(),
+                        ws.data_ptr(), nbytes, stream)
+    _lib.check(rc, "lm_pq_scan")
+    return dist, labels
+
+
 def flat_graph(g: HnswCsr, x) -> HnswCsr:
     """Single-level (Vamana-style) graph from the level-0 lists of ``g``, entered at the medoid
     (the node closest to the mean; DiskANN's `<prefix>_disk.index_medoids.bin`).  ``x``: [N, D] numpy array or torch tensor
