@@ -173,7 +173,7 @@ int lm_index_set_profiling(lm_index *idx, int32_t enable); /* HIP events around 
 int lm_index_event_overhead_us(lm_index *idx, double *out_us);
 /* Tuning knobs (A/B measurements): "update_variant" 0 = auto (default), 3 / 4 = the fused distance + beam-update kernel with a
  * wave / a workgroup per query.  "persistent_table" 1 (default) = stored-embedding searches run as ONE persistent
- * launch per batch, 0 = lock-step rounds; "persistent_wave" -1 (auto) / 0 / 1 = its workgroup- or wave-per-query form.
+ * launch per batch, 0 = lock-step rounds (a FILTERED stored-table search, lm_index_search_filtered*, runs the lock-step rounds whatever this says); "persistent_wave" -1 (auto) / 0 / 1 = its workgroup- or wave-per-query form.
  * "pq_threads" 256 / 512 / 1024 (default) = workgroup width of the PQ traversal.  "memo_initial_rows" = first allocation of the
  * per-call recompute memo in rows (0 = default: max(65536, 1024 per query of the pass)); it doubles on demand, never beyond N.
  * "pq_rerank_expanded" 0 (default) / 1: which set the DiskANN-style path's exact rerank ranks -- 0 the final candidate list (what
@@ -187,7 +187,8 @@ int lm_index_event_overhead_us(lm_index *idx, double *out_us);
  * also embeds the unvisited neighbours of the S best candidates that are not expanded yet, into the per-call memo, so that later rounds
  * find their new nodes there and need no forward (a one-query search is ~100 rounds of ~50 dependent launches: launch latency).  Labels,
  * distances and distance-evaluation counts are those of S = 0; only the provider's request lists differ (more ids in fewer calls).
- * lm_index_get_option reads a value back ("pq_rerank_overflow": queries that fell back since the option was last set). */
+ * lm_index_get_option reads a value back ("pq_rerank_overflow": queries that fell back since the option was last set;
+ * "filtered_allowed_evals": see lm_index_search_filtered). */
 int lm_index_set_option(lm_index *idx, const char *name, int64_t value);
 int lm_index_get_option(const lm_index *idx, const char *name, int64_t *value);
 
@@ -298,6 +299,42 @@ int lm_exact_search(const void *d_table, int32_t dtype, int64_t ntable, int32_t 
 int lm_index_search_exact(lm_index *idx, int64_t n, const float *x, int32_t k, const uint32_t *allow, float *distances, int64_t *labels);
 int lm_index_search_exact_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const uint32_t *d_allow, float *d_distances,
                                  int64_t *d_labels);
+/* Filtered graph search: lm_index_search with an allow-list, for the index that has neither a stored table (lm_index_search_exact) nor PQ codes
+ * (lm_pq_flat_search) -- a pruned HNSW graph searched with selective recompute -- and for any other index lm_index_search serves.  faiss filters
+ * inside the graph search (HNSW::search_from_candidates with an IDSelector): every evaluated node steers the walk, only selected nodes enter the
+ * result heap.  The reference filters AFTER the search (leann/api.py:785-790) and keeps what is left of the pool.  (csrc/lm_filter_impl.h)
+ *   allow / d_allow   lm_exact_search's layout and rules: NULL = every node, else ceil(ntotal / 32) words, ONE bitmap for the whole call; node i may
+ *                     enter the result iff bit i & 31 of word i >> 5 is set; bits at positions >= ntotal are ignored, whatever their value.  The
+ *                     host form takes a HOST array, uploaded per call into a buffer the index owns and grows; the device form borrows the caller's.
+ * Contract.  For each query let E be the set of nodes whose exact distance the level-0 beam search evaluates: the seed that the upper-level
+ * descent hands to level 0, and every node that enters a new-list while the query is in its beam phase (dynamic batching's extra pops
+ * included).  Nodes evaluated only during the upper-level descent are not in E.  The result is the best k of E n allowed under the key (internal
+ * distance, id) ascending -- NaN ranks as +inf, -0 as +0, ties go to the lower id --, decoded as lm_index_search decodes a pool key (ip: the
+ * negation, so an inner product of exactly 0 comes back as -0.0); slots beyond |E n allowed| get label -1 and +inf (L2) / -inf (ip).
+ * The walk is exactly that of lm_index_search with the same params: pops, stop rules, batch_size, beam_size, the memo, the hub cache and
+ * "speculate" -- the allow-list never influences it.  Hence
+ *   1. with allow == NULL or a bitmap of all ones, labels and distance bits are those of lm_index_search (its pool keeps the best
+ *      max(efSearch, k) of E);
+ *   2. with any allow-list, ndis, nexpand, nrounds, nunique and the provider's per-round request lists are those of lm_index_search;
+ *   3. a query's result does not depend on the other queries of the call, nor on how max_batch cuts the call into passes.
+ * A selective filter can still return FEWER than k hits: only nodes the walk evaluates can be returned, and the walk goes where the query
+ * is, not where the allowed nodes are.  The remedy is a larger efSearch, or lm_index_search_exact / lm_pq_flat_search where the index has a
+ * table / PQ codes: those rank every allowed row.
+ * Both sources: params->recompute = 1 (provider: with and without the per-call memo, with a hub cache, built-in or foreign provider) and
+ * recompute = 0 (attached fp32 / fp16 table; the lock-step rounds, not the persistent launch).  Each allowed node's distance is computed a
+ * second time by the collecting kernel, from the row the round has just fetched.
+ * Rejections come before anything is staged or launched, the outputs stay untouched: LM_EINVAL for everything lm_index_search rejects (NULL
+ * index / params / buffer, n < 0, k < 1, efSearch < 1, batch_size < 0) and for pq_pruning_ratio > 0 (the two-level search does not evaluate
+ * every new node exactly: E is not defined there); LM_ESTATE as for lm_index_search (recompute without a provider, recompute = 0 without a
+ * table).  n == 0: LM_OK.  An empty index: every slot gets the empty values.
+ * Stats: lm_index_get_stats as after lm_index_search (same meaning, same values -- nrounds included: where lm_index_search would run the
+ * persistent stored-table launch, a call cut into passes by max_batch reports its longest pass there and here);  lm_index_get_option(idx, "filtered_allowed_evals", &v) reads,
+ * for the last filtered call, the number of (query, node) pairs that passed the allow test = the sum of |E n allowed| over the queries.
+ * The index owns the result lists' workspace, apart from the other paths'. */
+int lm_index_search_filtered(lm_index *idx, int64_t n, const float *x, int32_t k, const uint32_t *allow, float *distances, int64_t *labels,
+                             const lm_search_params *params);
+int lm_index_search_filtered_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const uint32_t *d_allow, float *d_distances,
+                                    int64_t *d_labels, const lm_search_params *params);
 /* Flat PQ scan: the L best rows of an N x m code array by ADC distance, with an allow-list -- the filtered search of an index that stores no
  * embeddings (it keeps its PQ codes and the recompute provider).  No graph is walked, so a filter cannot disconnect it, and the allow-list is
  * part of the scan: rejected rows are never loaded.  (csrc/lm_pq_flat_impl.h)

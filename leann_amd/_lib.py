@@ -112,6 +112,7 @@ EXPORTED_SYMBOLS = [
     "lm_index_get_stats", "lm_index_set_profiling", "lm_index_set_option", "lm_index_get_option", "lm_index_event_overhead_us",
     "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
     "lm_exact_search", "lm_exact_search_workspace_bytes", "lm_index_search_exact", "lm_index_search_exact_device",
+    "lm_index_search_filtered", "lm_index_search_filtered_device",
     "lm_pq_scan", "lm_pq_scan_workspace_bytes", "lm_pq_flat_search", "lm_pq_flat_search_device",
     "lm_pq_attach", "lm_pq_attach_chunked", "lm_pq_search_params_default", "lm_pq_batch_search", "lm_pq_batch_search_device",
     "lm_add_layernorm_f16", "lm_attn_varlen_hd32_f16", "lm_attn_varlen_f16", "lm_embed_layernorm_f16", "lm_meanpool_varlen_f16",
@@ -174,6 +175,8 @@ def load() -> C.CDLL:
     lib.lm_exact_search.argtypes = [vp, i32, i64, i32, i32, vp, i64, i32, vp, vp, vp, vp, C.c_size_t, vp]
     lib.lm_index_search_exact.argtypes = [vp, i64, vp, i32, vp, vp, vp]
     lib.lm_index_search_exact_device.argtypes = [vp, i64, vp, i32, vp, vp, vp]
+    lib.lm_index_search_filtered.argtypes = [vp, i64, vp, i32, vp, vp, vp, C.POINTER(SearchParams)]
+    lib.lm_index_search_filtered_device.argtypes = [vp, i64, vp, i32, vp, vp, vp, C.POINTER(SearchParams)]
     lib.lm_pq_scan_workspace_bytes.argtypes = [i64, i64, i32, i32]
     lib.lm_pq_scan_workspace_bytes.restype = C.c_size_t
     lib.lm_pq_scan.argtypes = [vp, i64, i32, vp, vp, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp, C.c_size_t, vp]

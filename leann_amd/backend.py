@@ -383,13 +383,19 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
         reference filters after its search (leann/api.py:785-790) and returns fewer.  Slots without a row are label "-1", as from the graph search.
         ``pq_flat=True`` (keyword, default off; needs a product quantiser: build with ``pq_bytes=...``): the filtered search of a pruned index
         (lm_pq_flat_search) -- a flat PQ-ADC scan of the allowed rows keeps the ``complexity`` best, which are re-ranked exactly through the
-        recompute provider in one call (``recompute_embeddings=True``) or through the stored table (``False``; refused on a pruned index)."""
+        recompute provider in one call (``recompute_embeddings=True``) or through the stored table (``False``; refused on a pruned index).
+        ``graph_filter=True`` (keyword, default off; any index the graph search serves, ``recompute_embeddings`` True or False): the graph
+        search with ``allowed_ids`` as its allow-list (lm_index_search_filtered) -- the walk is the unfiltered one, the result is the best
+        ``top_k`` of the ALLOWED nodes it evaluated; a selective filter can still return fewer than ``top_k`` (raise ``complexity``, or use
+        ``exact`` / ``pq_flat`` where the index has a table / PQ codes).  Without ``allowed_ids`` it is the plain graph search."""
         exact, allowed_ids = bool(kwargs.get("exact", False)), kwargs.get("allowed_ids")
         pq_flat = bool(kwargs.get("pq_flat", False))
-        if allowed_ids is not None and not (exact or pq_flat):
-            raise ValueError("allowed_ids needs exact=True or pq_flat=True: the graph kernels take no filter")
-        if exact and pq_flat:
-            raise ValueError("exact=True and pq_flat=True are two different searches: choose one")
+        graph_filter = bool(kwargs.get("graph_filter", False))
+        if allowed_ids is not None and not (exact or pq_flat or graph_filter):
+            raise ValueError("allowed_ids needs exact=True or pq_flat=True: the graph kernels take no filter (or graph_filter=True: the graph "
+                             "search collects the allowed nodes it evaluates)")
+        if exact + pq_flat + graph_filter > 1:
+            raise ValueError("exact=True, pq_flat=True and graph_filter=True are different searches: choose one")
         if (not recompute_embeddings or exact) and (self.is_pruned or (exact and recompute_embeddings)):
             raise RuntimeError(
                 "Recompute is required for pruned/compact HNSW index. "
@@ -432,7 +438,10 @@ class Mi355xSearcher(LeannBackendSearcherInterface):
 
             idx.set_stream(torch.cuda.current_stream(self._torch_device()).cuda_stream)
         t0 = time.time()
-        distances, labels = idx.search(np.ascontiguousarray(query), int(top_k), params)
+        if graph_filter and allowed_ids is not None:
+            distances, labels = idx.search_filtered(np.ascontiguousarray(query), int(top_k), params, allowed=allowed_ids)
+        else:
+            distances, labels = idx.search(np.ascontiguousarray(query), int(top_k), params)
         logger.info(f"  Search time in Mi355xSearcher.search() backend: {time.time() - t0} seconds")
         string_labels = [[str(int(l)) for l in row] for row in labels]
         return {"labels": string_labels, "distances": distances}

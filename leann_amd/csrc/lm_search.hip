@@ -13,6 +13,7 @@
 //   lm_pq_impl.h  DiskANN-style path: k_pq_traverse (persistent PQ-ADC traversal), k_pq_rerank
 //   lm_select_impl.h  index build time: k_select_neighbors (HNSW select-neighbours heuristic, 16 lanes per row)
 //   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
+//   lm_filter_impl.h  allow-list for the graph search (lm_index_search_filtered*): k_filter_collect, once per lock-step round before k_update
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
@@ -40,6 +41,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 #include "lm_kernels_update.h"
 #include "lm_kernels_persist.h"
 #include "lm_kernels_misc.h"
+#include "lm_filter_impl.h"
 
 
 // =============================================================================================
@@ -109,6 +111,11 @@ struct lm_index {
     void* d_pqflat_ws = nullptr;
     uint32_t* d_pqflat_allow = nullptr;
     size_t pqflat_ws_bytes = 0, pqflat_allow_bytes = 0;
+    // lm_index_search_filtered*: the per-pass result lists and per-query counts, and the uploaded allow-list, grown on demand, apart from the other paths' workspaces
+    void* d_filter_ws = nullptr;
+    uint32_t* d_filter_allow = nullptr;
+    size_t filter_ws_bytes = 0, filter_allow_bytes = 0;
+    int64_t filtered_allowed_evals = 0;  // option "filtered_allowed_evals" (read only): (query, node) pairs of the last filtered call that passed the allow test
     std::vector<int32_t> h_pq_chunk_off;  // host copy of d_pq_chunk_off (m + 1)
     unsigned long long* h_counters = nullptr;  // pinned
     // stats / profiling
@@ -279,6 +286,53 @@ static int launch_update(lm_index* ix, const UpdateArgs& a, bool f16) {
     return f16 ? launch_update_nch<false, true>(ix, a, shmem) : launch_update_nch<false, false>(ix, a, shmem);
 }
 
+// lm_index_search_filtered*: what search_pass collects next to the walk (absent on every other call path)
+struct FilterPass {
+    const uint32_t* d_allow;  // NULL = every node
+    bool rounds_max = false;  // nrounds of a call cut into passes: the longest pass (what the persistent launch reports) instead of the sum
+};
+
+// the filtered search's result lists res[B][k], list lengths and per-query counts (+ their sum) in one allocation of the index's own
+static int ensure_filter_ws(lm_index* ix, int32_t B, int32_t k, FilterDev& f) {
+    const size_t res_bytes = (size_t)B * k * 8, cnt_bytes = ((size_t)B + 1) * 8, len_bytes = (size_t)B * 4;
+    const size_t need = res_bytes + cnt_bytes + len_bytes;
+    if (need > ix->filter_ws_bytes) {
+        if (ix->d_filter_ws) (void)hipFree(ix->d_filter_ws);
+        ix->d_filter_ws = nullptr;
+        ix->filter_ws_bytes = 0;
+        LM_HIP(hipMalloc(&ix->d_filter_ws, need));
+        ix->filter_ws_bytes = need;
+    }
+    unsigned char* p = (unsigned char*)ix->d_filter_ws;
+    f.res = (uint64_t*)p;
+    f.nallow = (unsigned long long*)(p + res_bytes);
+    f.nres = (int32_t*)(p + res_bytes + cnt_bytes);
+    f.k = k;
+    return LM_OK;
+}
+
+static int launch_filter_collect(lm_index* ix, const UpdateArgs& a, bool f16, const FilterDev& f) {
+    // LDS: list | merged list | survivors = (2 k + next_pow2(maxnew)) * 8 bytes.  That is never more than k_update needs at ef = max(efSearch, k),
+    // so the 64 KiB check of search_pass covers it.
+    const size_t shmem = (size_t)(2 * f.k + next_pow2(ix->ws.maxnew)) * sizeof(uint64_t);
+    const dim3 grid(ix->ws.B), block(256);
+    const bool l2 = ix->metric == LM_METRIC_L2;
+    switch (ix->Dp / 64) {
+#define CASEF(n)                                                                                                            \
+    case n:                                                                                                                 \
+        if (l2 && f16) hipLaunchKernelGGL((k_filter_collect<n, true, true>), grid, block, shmem, ix->stream, ix->ws, a, f);   \
+        else if (l2) hipLaunchKernelGGL((k_filter_collect<n, true, false>), grid, block, shmem, ix->stream, ix->ws, a, f);    \
+        else if (f16) hipLaunchKernelGGL((k_filter_collect<n, false, true>), grid, block, shmem, ix->stream, ix->ws, a, f);   \
+        else hipLaunchKernelGGL((k_filter_collect<n, false, false>), grid, block, shmem, ix->stream, ix->ws, a, f);           \
+        break
+        CASEF(1); CASEF(2); CASEF(3); CASEF(4); CASEF(5); CASEF(6); CASEF(8); CASEF(12); CASEF(16);
+#undef CASEF
+        default: LM_FAIL(LM_EINVAL, "unsupported padded dimension (supported: 64..384, 512, 768, 1024)");
+    }
+    LM_HIP(hipGetLastError());
+    return LM_OK;
+}
+
 // wave (64 threads) or workgroup (256 threads) per query for the persistent stored-embedding search: option "persistent_wave"
 // 1 / 0 forces either, -1 (default) = wave when the expected new-list per hop (beam x mean level-0 degree) fits one pass of a
 // wave's row groups comfortably (<= 24) and there are enough queries to fill the chip with waves (B >= 2048)
@@ -361,8 +415,9 @@ static int search_pass_persistent(lm_index* ix, int32_t B, const float* d_q, int
 }
 
 // one pass over <= max_batch queries; d_q: B x Dp (padded)
+// flt (lm_index_search_filtered* only): k_filter_collect runs in front of every k_update and the result comes from its lists, not from the pool
 static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, const lm_search_params& prm,
-                       float* d_dist, int64_t* d_labels) {
+                       float* d_dist, int64_t* d_labels, const FilterPass* flt = nullptr) {
     const int32_t ef = std::max(prm.efSearch, k);  // faiss: max(efSearch, k)
     const int32_t W = std::max(prm.beam_size, 1);
     const bool prune = prm.pq_pruning_ratio > 0.0f;
@@ -429,6 +484,12 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     LM_HIP(hipMemsetAsync(ws.visited, 0, (size_t)B * ws.nw * 4, st));
     LM_HIP(hipMemsetAsync(ws.counters, 0, C_NCOUNTERS * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_init, dim3((B + 255) / 256), dim3(256), 0, st, ws, ix->max_level);
+    FilterDev fd{};
+    if (flt) {
+        if ((rc = ensure_filter_ws(ix, B, k, fd)) != LM_OK) return rc;
+        fd.allow = flt->d_allow;
+        hipLaunchKernelGGL(k_filter_init, dim3((B + 255) / 256), dim3(256), 0, st, fd, B);
+    }
 
     UpdateArgs ua{};
     unsigned long long* span_acc = nullptr;
@@ -512,11 +573,13 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
                 ua.E = d_e;
                 ua.by_rank = 1;
             }
+            if (flt && (rc = launch_filter_collect(ix, ua, false, fd)) != LM_OK) return rc;
             EvScope es(ix, &ix->ev_update);
             rc = launch_update(ix, ua, false);
         } else {
             ua.E = ix->d_table;
             ua.by_rank = 0;
+            if (flt && (rc = launch_filter_collect(ix, ua, ix->table_dtype == LM_DTYPE_F16, fd)) != LM_OK) return rc;
             EvScope es(ix, &ix->ev_update);
             rc = launch_update(ix, ua, ix->table_dtype == LM_DTYPE_F16);
         }
@@ -527,12 +590,23 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
         if (span_acc) hipLaunchKernelGGL(k_span, dim3(1), dim3(256), 0, st, ix->d_tstamp, B, span_acc);
         ix->stats.update_launches++;
     }
-    hipLaunchKernelGGL(k_finalize, dim3((B * k + 255) / 256), dim3(256), 0, st, ws, k, ix->metric, d_labels, d_dist);
+    if (flt) {
+        hipLaunchKernelGGL(k_filter_finalize, dim3((B * k + 255) / 256), dim3(256), 0, st, fd, B, ix->metric, d_labels, d_dist);
+        hipLaunchKernelGGL(k_filter_total, dim3(1), dim3(256), 0, st, fd, B);
+    } else {
+        hipLaunchKernelGGL(k_finalize, dim3((B * k + 255) / 256), dim3(256), 0, st, ws, k, ix->metric, d_labels, d_dist);
+    }
     hipLaunchKernelGGL(k_stats, dim3(1), dim3(256), 0, st, ws);
     LM_HIP(hipGetLastError());
     LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     LM_HIP(hipStreamSynchronize(st));
-    ix->stats.nrounds += (int64_t)hc[C_ROUNDS];
+    if (flt) {
+        unsigned long long total = 0;
+        LM_HIP(hipMemcpy(&total, fd.nallow + B, sizeof(total), hipMemcpyDeviceToHost));
+        ix->filtered_allowed_evals += (int64_t)total;
+    }
+    if (flt && flt->rounds_max) ix->stats.nrounds = std::max<int64_t>(ix->stats.nrounds, (int64_t)hc[C_ROUNDS]);
+    else ix->stats.nrounds += (int64_t)hc[C_ROUNDS];
     ix->stats.ndis += (int64_t)hc[C_NDIS];
     ix->stats.nexpand += (int64_t)hc[C_NEXPAND];
     ix->stats.nadc += (int64_t)hc[C_NADC];
@@ -565,13 +639,15 @@ static int ensure_stage(lm_index* ix, size_t need_x, size_t need_d, size_t need_
     return LM_OK;
 }
 
+// flt != NULL: lm_index_search_filtered* (the lock-step rounds with k_filter_collect); NULL: the launches are exactly those of the unfiltered search
 static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, float* d_dist, int64_t* d_labels,
-                            const lm_search_params* params) {
+                            const lm_search_params* params, const FilterPass* flt = nullptr) {
     if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
     lm_search_params prm = *params;
     if (prm.efSearch <= 0) LM_FAIL(LM_EINVAL, "efSearch must be positive");
     if (prm.batch_size < 0) LM_FAIL(LM_EINVAL, "batch_size must not be negative (0 = no dynamic batching)");
     LM_HIP(hipSetDevice(ix->device));
+    if (flt) ix->filtered_allowed_evals = 0;
     ix->stats = lm_search_stats{};
     ix->span_ms = 0;
     ix->span_launches = 0;
@@ -609,14 +685,27 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     // bound the visited bitmaps to 8 GiB
     int64_t nwbytes = ((ix->N + 31) / 32) * 4;
     maxb = std::max<int64_t>(1, std::min<int64_t>(maxb, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));
+    // the persistent launch's condition (search_pass_persistent declines when its LDS does not fit: its own check, restated for the filtered search)
+    const bool persistent = !prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table && ix->update_variant == 0 &&
+                            std::max(prm.beam_size, 1) <= 64;
+    FilterPass fpass{};
+    if (flt) {
+        // The stats of a filtered call are those of lm_index_search on the same inputs.  Where that call runs the persistent launch, its nrounds
+        // is the longest pass's, not the sum over the passes: report the same.
+        const int32_t maxnew = std::max({std::max(prm.beam_size, 1) * ix->maxdeg0, ix->maxdeg_up, 1});
+        fpass = *flt;
+        fpass.rounds_max = persistent && ((size_t)2 * std::max(prm.efSearch, k) + next_pow2(maxnew)) * 8 + (size_t)maxnew * 4 <= 150 * 1024;
+        flt = &fpass;
+    }
     for (int64_t off = 0; off < n; off += maxb) {
         int32_t B = (int32_t)std::min<int64_t>(maxb, n - off);
         int rc = 1;
         // (dynamic batching exists to fill the recompute forward: a stored-embedding search that asks for it runs the lock-step kernels, which implement it)
-        if (!prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table && ix->update_variant == 0 && std::max(prm.beam_size, 1) <= 64)
+        // (a filtered search collects its result round by round: lock-step too)
+        if (!flt && persistent)
             rc = search_pass_persistent(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k);
         if (rc == 1)  // not applicable (or LDS budget exceeded): lock-step rounds
-            rc = search_pass(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k);
+            rc = search_pass(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k, flt);
         if (rc) return rc;
     }
     LM_HIP(hipStreamSynchronize(st));
@@ -783,6 +872,8 @@ void lm_index_free(lm_index* ix) {
     if (ix->d_exact_allow) (void)hipFree(ix->d_exact_allow);
     if (ix->d_pqflat_ws) (void)hipFree(ix->d_pqflat_ws);
     if (ix->d_pqflat_allow) (void)hipFree(ix->d_pqflat_allow);
+    if (ix->d_filter_ws) (void)hipFree(ix->d_filter_ws);
+    if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
     if (ix->h_counters) (void)hipHostFree(ix->h_counters);
     (void)drain_events(ix, ix->ev_update);
     (void)drain_events(ix, ix->ev_expand);
@@ -951,6 +1042,7 @@ int lm_index_get_option(const lm_index* ix, const char* name, int64_t* value) {
     else if (!std::strcmp(name, "speculate")) *value = ix->speculate;
     else if (!std::strcmp(name, "single_query_direct")) *value = ix->single_query_direct;
     else if (!std::strcmp(name, "speculate_max_batch")) *value = ix->speculate_max_batch;
+    else if (!std::strcmp(name, "filtered_allowed_evals")) *value = ix->filtered_allowed_evals;
     else LM_FAIL(LM_EINVAL, std::string("unknown readable option: ") + name);
     return LM_OK;
 }
@@ -1029,6 +1121,60 @@ int lm_index_search(lm_index* ix, int64_t n, const float* x, int32_t k, float* d
         rc = LM_EHIP;
     }
     return rc;
+}
+
+// Everything lm_index_search_filtered* rejects, in front of any staging or launch (do_search_device repeats the argument checks; the order --
+// arguments, n == 0, the empty index, the state -- is lm_index_search's).
+static int filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm_search_params* params) {
+    if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
+    if (params->efSearch <= 0) LM_FAIL(LM_EINVAL, "efSearch must be positive");
+    if (params->batch_size < 0) LM_FAIL(LM_EINVAL, "batch_size must not be negative (0 = no dynamic batching)");
+    if (params->pq_pruning_ratio > 0.0f)
+        LM_FAIL(LM_EINVAL, "the filtered graph search takes no pq_pruning_ratio: the two-level search does not evaluate every new node exactly");
+    if (n == 0 || ix->N == 0 || ix->entry_point < 0) return LM_OK;  // nothing to walk: LM_OK whatever is attached
+    if (params->recompute) {
+        if (!ix->provider) LM_FAIL(LM_ESTATE, "recompute requested but no embedding provider is attached");
+    } else if (!ix->d_table) {
+        LM_FAIL(LM_ESTATE, "index stores no embeddings (pruned): recompute is required");
+    }
+    return LM_OK;
+}
+
+int lm_index_search_filtered_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const uint32_t* d_allow, float* d_distances,
+                                    int64_t* d_labels, const lm_search_params* params) {
+    if (int rc = filtered_checks(ix, n, k, params)) return rc;
+    if (n > 0 && (!d_x || !d_distances || !d_labels)) LM_FAIL(LM_EINVAL, "NULL buffer");
+    const FilterPass flt{d_allow};
+    return do_search_device(ix, n, d_x, k, d_distances, d_labels, params, &flt);
+}
+
+int lm_index_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t k, const uint32_t* allow, float* distances, int64_t* labels,
+                             const lm_search_params* params) {
+    if (int rc = filtered_checks(ix, n, k, params)) return rc;
+    FilterPass flt{nullptr};
+    if (n == 0) return do_search_device(ix, 0, nullptr, k, nullptr, nullptr, params, &flt);  // the stats of an empty call
+    if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
+    LM_HIP(hipSetDevice(ix->device));
+    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
+    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
+    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
+    if (allow) {
+        if (allow_bytes > ix->filter_allow_bytes) {
+            if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
+            ix->d_filter_allow = nullptr;
+            ix->filter_allow_bytes = 0;
+            LM_HIP(hipMalloc((void**)&ix->d_filter_allow, std::max<size_t>(allow_bytes, 16)));
+            ix->filter_allow_bytes = std::max<size_t>(allow_bytes, 16);
+        }
+        flt.d_allow = ix->d_filter_allow;
+        if (allow_bytes) LM_HIP(hipMemcpyAsync(ix->d_filter_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
+    }
+    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
+    if (int rc = do_search_device(ix, n, ix->d_stage_x, k, ix->d_stage_d, ix->d_stage_l, params, &flt)) return rc;
+    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipStreamSynchronize(ix->stream));
+    return LM_OK;
 }
 
 int lm_dist_gather(const void* d_table, int32_t dtype, int32_t d_padded, int32_t metric, const float* d_q,

@@ -217,6 +217,45 @@ class Mi355xIndex:
         self._raise_provider(rc, "lm_index_search_device")
         return dist, labels
 
+    # ---- graph search with an allow-list ----------------------------------------------------------
+    def search_filtered(self, queries: np.ndarray, k: int, params: SearchParams, allowed=None):
+        """:meth:`search` with an allow-list (lm_index_search_filtered): the same walk, the best k of the ALLOWED nodes it evaluated; (distances,
+        labels) numpy, slots without a node -1 / +-inf.  ``allowed``: None (= :meth:`search`'s result), a bool mask [ntotal] or an array of ids."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.info.d:
+            raise ValueError(f"query must be (B, {self.info.d}) float32")
+        n = q.shape[0]
+        dist = np.empty((n, k), dtype=np.float32)
+        labels = np.empty((n, k), dtype=np.int64)
+        words = None if allowed is None else allow_bitmap(allowed, int(self.info.ntotal))
+        rc = self._lib.lm_index_search_filtered(self._h, n, _np_ptr(q), k, None if words is None else _np_ptr(words), _np_ptr(dist), _np_ptr(labels),
+                                                C.byref(params))
+        self._raise_provider(rc, "lm_index_search_filtered")
+        return dist, labels
+
+    def search_filtered_device(self, queries, k: int, params: SearchParams, allowed=None):
+        """The same with ``queries`` a CUDA/HIP torch tensor (B, D) f32; returns torch tensors.  ``allowed`` as for :meth:`search_filtered`, or a
+        device int32 tensor that already holds the bitmap words."""
+        import torch
+
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        n = queries.shape[0]
+        dist = torch.empty((n, k), dtype=torch.float32, device=queries.device)
+        labels = torch.empty((n, k), dtype=torch.int64, device=queries.device)
+        words = None
+        if allowed is not None:
+            if isinstance(allowed, torch.Tensor) and allowed.is_cuda and allowed.dtype == torch.int32:
+                words = allowed.contiguous()
+                if words.numel() != (int(self.info.ntotal) + 31) // 32:
+                    raise ValueError("a device bitmap must hold ceil(ntotal / 32) int32 words")
+            else:
+                host = allowed.cpu().numpy() if isinstance(allowed, torch.Tensor) else allowed
+                words = torch.from_numpy(allow_bitmap(host, int(self.info.ntotal)).view(np.int32)).to(queries.device)
+        rc = self._lib.lm_index_search_filtered_device(self._h, n, C.c_void_p(queries.data_ptr()), k, None if words is None else C.c_void_p(words.data_ptr()),
+                                                       C.c_void_p(dist.data_ptr()), C.c_void_p(labels.data_ptr()), C.byref(params))
+        self._raise_provider(rc, "lm_index_search_filtered_device")
+        return dist, labels
+
     # ---- exact search over the attached table -----------------------------------------------------
     def search_exact(self, queries: np.ndarray, k: int, allowed=None):
         """Exact top-k of the attached table (lm_index_search_exact == oracle bruteforce_topk + allow-list): (distances, labels) numpy,
