@@ -267,6 +267,47 @@ int lm_topk_merge(const int64_t *d_in_ids, const float *d_in_dist, int32_t S, in
 int lm_select_neighbors(const void *d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric,
                         const int32_t *d_cand, const float *d_dist, int64_t n, int32_t K, int32_t m, float alpha,
                         uint8_t *d_keep, void *stream);
+/* Index build time: link insertion.  faiss links every inserted node inside index.add (HNSW::add_link, which calls shrink_neighbor_list on
+ * a list that overflows; leann_backend_hnsw/hnsw_backend.py:66-94); the batched builder adds a whole batch's forward and reverse edges at
+ * once.  This call merges the directed edges src -> dst into the affected rows of one level's fixed-capacity adjacency, IN PLACE.
+ * (csrc/lm_link_impl.h)
+ *   d_table [n][d_padded]   fp32 or fp16 rows, zero padded (lm_select_neighbors' layout); row i = the vector of node i of this level;
+ *   d_adj   [n][cap]        the level's adjacency; a slot value outside [0, n) is EMPTY (holes are tolerated);
+ *   d_dist  [n][cap]        the INTERNAL distances of its links (squared L2, or -ip: smaller is closer);
+ *   d_deg   [n]             OUTPUT only: the number of links of every row this call rewrites;
+ *   d_src / d_dst / d_w [ne]   the edges to add; d_w holds internal distances, taken as given, not recomputed.
+ * An edge is INVALID when src or dst is outside [0, n) or src == dst: it is ignored and never dereferenced.  A row is AFFECTED when it is
+ * the src of at least one valid edge.  For every affected row v:
+ *   1. Candidates: the non-empty slots c = 0 .. cap-1 of row v in slot order, each with d_dist[v][c]; then the valid edges e with
+ *      src[e] == v in ascending e, each with d_w[e].
+ *   2. Dedupe by dst, the first occurrence wins: an existing entry beats any incoming edge, among incoming edges the lowest e wins; the
+ *      loser's weight is discarded even if it is smaller.
+ *   3. Order by the key (internal distance, dst) ascending: NaN ranks as +inf, -0 as +0, ties go to the lower dst.
+ *   4. Truncate to the first 2 * cap.
+ *   5. If at most cap remain they are the new list as they stand (no selection, even if one dominates another: faiss add_link).  Otherwise
+ *      the new list is what lm_select_neighbors' rule keeps with K = 2 * cap, m = cap on these candidates and their distances in this
+ *      order: the strict pass, then the relaxed pass when alpha != 1; pairwise distances by the canonical reduction orc_dist, fp32
+ *      throughout, no contraction.
+ *   6. The kept entries go left-packed, in order, into d_adj[v] / d_dist[v] -- every distance with the bits it came with (a NaN stays that
+ *      NaN, -0 stays -0) --, the remaining slots get -1 and +inf, d_deg[v] = the count.
+ * Rows that are not affected are not written: every byte of their d_adj, d_dist and d_deg stays.  The result is a function of the input
+ * bits alone (not of the order in which atomics land or rows are scheduled); no floating-point atomics.
+ * A row may receive any number of edges.  LM_LINK_STAGE edges of a row are staged on chip at a time; larger rows take more passes over
+ * their bucket and are just as exact.
+ * Workspace: lm_graph_add_links_workspace_bytes(n, ne), a pure function of its arguments (0 for arguments the call rejects, and when
+ * n == 0 or ne == 0: nothing is needed then).  d_workspace must be 4-byte aligned (it is carved into int32 / float arrays at multiples
+ * of 256 bytes from its base; any hipMalloc'ed pointer is).
+ * Cost that does not depend on the edges: one 1024-lane workgroup walks all n row counters on every call (1024 rows per step), and the row
+ * kernel's grid is min(n, ne) workgroups, of which those beyond the number of affected rows leave at once.  Neither is measured yet at
+ * n >> 1M; the builder calls this with n = one level's node count.
+ * LM_EINVAL (before anything is launched, the buffers untouched): d_padded % 64 != 0 or a width the search kernels do not cover, unknown
+ * dtype or metric, cap < 1 or 2 * cap > LM_SELECT_MAX_K, alpha < 1 or not finite, negative n or ne, n or ne > INT32_MAX, a NULL buffer
+ * where one is needed, a d_workspace that is not 4-byte aligned, workspace_bytes below lm_graph_add_links_workspace_bytes(n, ne).  ne == 0 or n == 0: LM_OK, nothing is written. */
+#define LM_LINK_STAGE 128
+size_t lm_graph_add_links_workspace_bytes(int64_t n, int64_t ne);
+int lm_graph_add_links(const void *d_table, int32_t dtype, int32_t d_padded, int32_t metric, int32_t *d_adj, float *d_dist,
+                       int32_t *d_deg, int64_t n, int32_t cap, const int32_t *d_src, const int32_t *d_dst, const float *d_w, int64_t ne,
+                       float alpha, void *d_workspace, size_t workspace_bytes, void *stream);
 /* Exact top-k over a stored-embedding table = oracle/lm_oracle.c:orc_bruteforce_topk (the paper's IndexFlatIP baseline) plus an allow-list.  The
  * reference has no such path: leann/api.py:785-790 applies metadata_filters AFTER the graph search, so a filtered query returns fewer than top_k
  * hits; here the filter is part of the scan and the result is the best k of the allowed rows.  (csrc/lm_exact_impl.h)

@@ -20,6 +20,7 @@ DTYPE_F32, DTYPE_F16 = 0, 1
 SELECT_MAX_K = 512  # include/leann_mi355x.h: LM_SELECT_MAX_K
 PQ_MAX_SUB = 64  # include/leann_mi355x.h: LM_PQ_MAX_SUB
 EXACT_MAX_K = 256  # include/leann_mi355x.h: LM_EXACT_MAX_K
+LINK_STAGE = 128  # include/leann_mi355x.h: LM_LINK_STAGE
 PQ_FLAT_MAX_L = 1024  # include/leann_mi355x.h: LM_PQ_FLAT_MAX_L
 
 
@@ -110,7 +111,7 @@ EXPORTED_SYMBOLS = [
     "lm_index_attach_table", "lm_index_set_provider", "lm_index_set_hub_cache", "lm_index_set_stream",
     "lm_search_params_default", "lm_index_search", "lm_index_search_device",
     "lm_index_get_stats", "lm_index_set_profiling", "lm_index_set_option", "lm_index_get_option", "lm_index_event_overhead_us",
-    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
+    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_graph_add_links", "lm_graph_add_links_workspace_bytes", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
     "lm_exact_search", "lm_exact_search_workspace_bytes", "lm_index_search_exact", "lm_index_search_exact_device",
     "lm_index_search_filtered", "lm_index_search_filtered_device",
     "lm_pq_scan", "lm_pq_scan_workspace_bytes", "lm_pq_flat_search", "lm_pq_flat_search_device",
@@ -166,6 +167,9 @@ def load() -> C.CDLL:
     lib.lm_dist_gather.argtypes = [vp, i32, i32, i32, vp, vp, vp, i64, vp, vp]
     lib.lm_topk_merge.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
     lib.lm_select_neighbors.argtypes = [vp, i32, i64, i32, i32, vp, vp, i64, i32, i32, C.c_float, vp, vp]
+    lib.lm_graph_add_links_workspace_bytes.argtypes = [i64, i64]
+    lib.lm_graph_add_links_workspace_bytes.restype = C.c_size_t
+    lib.lm_graph_add_links.argtypes = [vp, i32, i32, i32, vp, vp, vp, i64, i32, vp, vp, vp, i64, C.c_float, vp, C.c_size_t, vp]
     lib.lm_pq_encode.argtypes = [vp, i32, i64, i32, i32, i32, vp, vp, vp, vp]
     lib.lm_pq_train.argtypes = [vp, i32, i64, i32, i32, i32, vp, i32, vp, vp, C.c_size_t, vp]
     lib.lm_pq_train_workspace_bytes.argtypes = [i64, i32, i32]

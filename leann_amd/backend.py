@@ -138,13 +138,15 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         batched GPU builder driven by the HIP search kernel (gpu_graph_build.py) -- minutes instead of hours at 1M-60M chunks.
         ``hub_preserving_m`` > 0 additionally applies the paper's high-degree-preserving pruning (Algorithm 3): ~m links per
         node, full lists for the 2 % hub nodes -- the storage side of a recompute (pruned) index.  ``gpu_select_kernel`` (bool, default
-        False): both of these pick neighbours with the library's kernel (lm_select_neighbors) instead of torch ops."""
+        False): both of these pick neighbours with the library's kernel (lm_select_neighbors) instead of torch ops.  ``gpu_link_kernel``
+        (bool, default False): both of these insert their links with the library's kernel (lm_graph_add_links) instead of torch ops."""
         from .hnsw_builder import build_hnsw
 
         bp = self.build_params
         thr = int(bp.get("gpu_build_threshold", 100_000))
         m_low = int(bp.get("hub_preserving_m", 0) or 0)
         selector = "kernel" if bool(bp.get("gpu_select_kernel", False)) else "torch"
+        linker = "kernel" if bool(bp.get("gpu_link_kernel", False)) else "torch"
         use_gpu = data.shape[0] >= thr and _lib.device_count() > 0
         if not use_gpu and m_low <= 0:
             return build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
@@ -154,15 +156,15 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
 
         if use_gpu:
             x = torch.from_numpy(np.ascontiguousarray(data)).to(torch.device("cuda", int(bp.get("device", 0))))
-            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector)
+            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker)
         else:
             x = torch.from_numpy(np.ascontiguousarray(data))
-            if selector == "kernel":  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)
+            if selector == "kernel" or linker == "kernel":  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)
                 _lib.require_gpu()
                 x = x.to(torch.device("cuda", int(bp.get("device", 0))))
             g = build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
         if m_low > 0:
-            g = prune_preserving_hubs(g, x, self.M, m_low, float(bp.get("hub_fraction", 0.02)), selector=selector)
+            g = prune_preserving_hubs(g, x, self.M, m_low, float(bp.get("hub_fraction", 0.02)), selector=selector, linker=linker)
         return g
 
 

@@ -14,6 +14,7 @@
 //   lm_select_impl.h  index build time: k_select_neighbors (HNSW select-neighbours heuristic, 16 lanes per row)
 //   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
 //   lm_filter_impl.h  allow-list for the graph search (lm_index_search_filtered*): k_filter_collect, once per lock-step round before k_update
+//   lm_link_impl.h    index build time: link insertion (lm_graph_add_links): k_link_count / k_link_scan / k_link_fill / k_link_row
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
@@ -1220,4 +1221,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_pq_build_impl.h"
 #include "lm_exact_impl.h"
 #include "lm_pq_flat_impl.h"
+#include "lm_link_impl.h"
 

@@ -200,18 +200,96 @@ def _selector_fn(selector: str):
     raise ValueError(f"selector must be one of {SELECTORS}, not {selector!r}")
 
 
-class _LevelGraph:
-    """Fixed-capacity adjacency of one level over the node subset ``sub`` (sorted global ids)."""
+LINKERS = ("torch", "kernel")
 
-    def __init__(self, sub: torch.Tensor, cap: int, selector: str = "torch"):
+
+def _check_linker(linker: str) -> str:
+    if linker not in LINKERS:
+        raise ValueError(f"linker must be one of {LINKERS}, not {linker!r}")
+    return linker
+
+
+class _LevelGraph:
+    """Fixed-capacity adjacency of one level over the node subset ``sub`` (sorted global ids).
+
+    ``linker``: how add_links merges new edges into the rows.  "torch" (default): the torch-op composition below, on int64 ids and
+    similarities (``adj`` / ``sim``).  "kernel": one call of lm_graph_add_links; the level then lives in the kernel's layout -- int32 ids
+    and fp32 INTERNAL distances (``adj`` / ``dist`` = -sim) --; add_links converts the call's edges only and rows() the rows asked for,
+    nothing whole (links(), once per level when the level below is seeded, and export(), as the torch layout's host copy, do).  The
+    kernel shrinks an overflowing list with the canonical fp32 rule of lm_select_neighbors whatever ``selector`` says (``selector``
+    then decides the builder's own selections only); with selector="kernel" both linkers give the same rows bit for bit.
+    The builder reads and writes rows through rows() / clear_rows() / seed_rows() / links() / export(), which serve both layouts."""
+
+    def __init__(self, sub: torch.Tensor, cap: int, selector: str = "torch", linker: str = "torch"):
         n = sub.shape[0]
         self._select = _selector_fn(selector)
+        self.linker = _check_linker(linker)
         self.sub = sub
         self.cap = cap
-        self.adj = torch.full((n, cap), -1, dtype=torch.int64, device=sub.device)
-        self.sim = torch.full((n, cap), -float("inf"), dtype=torch.float32, device=sub.device)
-        self.deg = torch.zeros((n,), dtype=torch.int64, device=sub.device)
+        if linker == "kernel":
+            self.adj = torch.full((n, cap), -1, dtype=torch.int32, device=sub.device)
+            self.dist = torch.full((n, cap), float("inf"), dtype=torch.float32, device=sub.device)
+            self.deg = torch.zeros((n,), dtype=torch.int32, device=sub.device)
+            self._ws = torch.empty((0,), dtype=torch.uint8, device=sub.device)  # lm_graph_add_links' workspace: grown, never shrunk
+        else:
+            self.adj = torch.full((n, cap), -1, dtype=torch.int64, device=sub.device)
+            self.sim = torch.full((n, cap), -float("inf"), dtype=torch.float32, device=sub.device)
+            self.deg = torch.zeros((n,), dtype=torch.int64, device=sub.device)
         self.alpha = 1.0  # neighbour-selection relaxation (_domination_threshold); build_graph_gpu(alpha=...) sets it
+
+    # ---- row access for the builder (ids int64, similarities fp32: larger is closer), whatever the layout
+    def rows(self, batch: torch.Tensor):
+        """(ids [b, cap] int64, sim [b, cap]) of the rows ``batch``."""
+        if self.linker == "kernel":
+            return self.adj[batch].to(torch.int64), -self.dist[batch]  # an exact negation
+        return self.adj[batch], self.sim[batch]
+
+    def clear_rows(self, batch: torch.Tensor):
+        self.adj[batch] = -1
+        if self.linker == "kernel":
+            self.dist[batch] = float("inf")
+        else:
+            self.sim[batch] = -float("inf")
+        self.deg[batch] = 0
+
+    def seed_rows(self, loc: torch.Tensor, ids: torch.Tensor, sim: torch.Tensor):
+        """Rows ``loc`` := (ids [b, cap] int64, -1 = empty, sim [b, cap])."""
+        if self.linker == "kernel":
+            self.adj[loc] = ids.to(torch.int32)
+            self.dist[loc] = -sim
+        else:
+            self.adj[loc], self.sim[loc] = ids, sim
+        self.deg[loc] = (ids >= 0).sum(1).to(self.deg.dtype)
+
+    def links(self):
+        """(ids [n, cap] int64, sim [n, cap]) of the whole level, on its device (the level below is seeded from them)."""
+        if self.linker == "kernel":
+            return self.adj.to(torch.int64), -self.dist
+        return self.adj, self.sim
+
+    def export(self) -> np.ndarray:
+        """The adjacency as a host array [n, cap] int64, -1 padded (what _assemble_csr reads)."""
+        a = self.adj.cpu().numpy()
+        return a.astype(np.int64) if a.dtype != np.int64 else a
+
+    @torch.no_grad()
+    def _add_links_kernel(self, xs: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, w: torch.Tensor, metric: int):
+        from . import _lib
+
+        lib = _lib.load()
+        tab = _padded_table(xs)  # callers pad once per level: then this is xs itself
+        n, ne = self.adj.shape[0], src.shape[0]
+        s32 = src.to(torch.int32).contiguous()
+        d32 = dst.to(torch.int32).contiguous()
+        dist = (-w.to(torch.float32)).contiguous()  # similarity -> internal distance
+        need = int(lib.lm_graph_add_links_workspace_bytes(n, ne))
+        if self._ws.numel() < need:
+            self._ws = torch.empty((need,), dtype=torch.uint8, device=self.adj.device)
+        stream = torch.cuda.current_stream(tab.device).cuda_stream if tab.is_cuda else None
+        rc = lib.lm_graph_add_links(tab.data_ptr(), _lib.DTYPE_F16 if tab.dtype == torch.float16 else _lib.DTYPE_F32, tab.shape[1], int(metric),
+                                    self.adj.data_ptr(), self.dist.data_ptr(), self.deg.data_ptr(), n, self.cap, s32.data_ptr(), d32.data_ptr(),
+                                    dist.data_ptr(), ne, float(self.alpha), self._ws.data_ptr(), self._ws.numel(), stream)
+        _lib.check(rc, "lm_graph_add_links")
 
     @torch.no_grad()
     def add_links(self, xs: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, w: torch.Tensor, metric: int):
@@ -219,6 +297,12 @@ class _LevelGraph:
         re-pruned with the heuristic (faiss shrink_neighbor_list)."""
         if src.numel() == 0:
             return
+        if self.linker == "kernel":
+            return self._add_links_kernel(xs, src, dst, w, metric)
+        return self._add_links_torch(xs, src, dst, w, metric)
+
+    @torch.no_grad()
+    def _add_links_torch(self, xs: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, w: torch.Tensor, metric: int):
         n, cap = self.adj.shape
         aff = torch.unique(src)
         # existing edges of the affected rows
@@ -340,13 +424,18 @@ def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
 @torch.no_grad()
 def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_construction: int = 200, seed: int = 12345,
                     search_fn: Optional[SearchFn] = None, growth: float = 1.5, k_cand: int = 0,
-                    seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch") -> HnswCsr:
+                    seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch",
+                    linker: str = "torch") -> HnswCsr:
     """x: [N, D] float tensor on the build device.  Returns the compact-CSR HNSW graph (host).  ``alpha`` > 1 relaxes the neighbour
     selection the way Vamana does (denser lists with longer edges: what a PQ-guided walk over a flat graph needs at 10M nodes -- DESIGN 8;
     inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on.
     ``selector``: "torch" (default) = neighbour selection by the vectorised torch ops, "kernel" = by lm_select_neighbors (canonical fp32
-    distances: a slightly different, oracle-pinned graph -- DESIGN.md)."""
+    distances: a slightly different, oracle-pinned graph -- DESIGN.md).
+    ``linker``: "torch" (default) = link insertion (_LevelGraph.add_links) by torch ops, "kernel" = by lm_graph_add_links.  The kernel
+    shrinks overflowing lists with the canonical fp32 rule whatever ``selector`` is; with selector="kernel" both linkers build the same
+    graph byte for byte."""
     select = _selector_fn(selector)
+    _check_linker(linker)
     metric = metric.lower()
     if metric not in ("mips", "cosine", "l2"):
         raise ValueError(f"Unsupported distance_metric '{metric}'.")
@@ -373,21 +462,22 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
         nl = sub.shape[0]
         xs = x[sub]
         xsel = _padded_table(xs) if selector == "kernel" else xs  # what the selector reads: padded once per level
+        xlink = _padded_table(xsel) if linker == "kernel" else xsel  # what add_links reads (the torch form hands it to the selector)
         cap = 2 * M if l == 0 else M
-        G = _LevelGraph(sub, cap, selector)
+        G = _LevelGraph(sub, cap, selector, linker)
         G.alpha = alpha
         inserted = torch.zeros(nl, dtype=torch.bool, device=dev)
         if finished and finished[0].sub.shape[0] >= 2:
             # seed with the level above (its nodes are a subset of this level)
             up = finished[0]
             loc = torch.searchsorted(sub, up.sub)
-            m = up.adj >= 0
-            a = torch.full((up.adj.shape[0], cap), -1, dtype=torch.int64, device=dev)
-            s = torch.full((up.adj.shape[0], cap), -float("inf"), device=dev)
-            a[:, : up.cap][m] = loc[up.adj[m]]
-            s[:, : up.cap][m] = up.sim[m]
-            G.adj[loc], G.sim[loc] = a, s
-            G.deg[loc] = m.sum(1)
+            up_adj, up_sim = up.links()
+            m = up_adj >= 0
+            a = torch.full((up_adj.shape[0], cap), -1, dtype=torch.int64, device=dev)
+            s = torch.full((up_adj.shape[0], cap), -float("inf"), device=dev)
+            a[:, : up.cap][m] = loc[up_adj[m]]
+            s[:, : up.cap][m] = up_sim[m]
+            G.seed_rows(loc, a, s)
             inserted[loc] = True
         else:
             ns = min(nl, seed_nodes)
@@ -400,7 +490,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 src = perm0[torch.arange(perm0.shape[0], device=dev)[:, None].expand_as(ci)[keep]]
                 dst = perm0[ci[keep]]
                 w = cs[keep]
-                G.add_links(xsel, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
+                G.add_links(xlink, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
             inserted[perm0] = True
         rest = torch.nonzero(~inserted).flatten()
         rest = rest[torch.randperm(rest.shape[0], generator=gen).to(dev)]
@@ -409,7 +499,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
         sub_np = sub.cpu().numpy()
 
         def temp_csr():
-            graphs = [(sub_np, G.adj.cpu().numpy())] + [(f.sub.cpu().numpy(), f.adj.cpu().numpy()) for f in finished]
+            graphs = [(sub_np, G.export())] + [(f.sub.cpu().numpy(), f.export()) for f in finished]
             return _assemble_csr(rel_top, graphs, sub_np, d, mt, entry_global, M, ef_construction)
 
         def insert(batch: torch.Tensor, replace: bool):
@@ -422,8 +512,9 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 selfm = ids == batch[:, None]
                 ids = ids.masked_fill(selfm, -1)
                 sim = sim.masked_fill(selfm, -float("inf"))
-                ids = torch.cat([ids, G.adj[batch]], 1)
-                sim = torch.cat([sim, G.sim[batch]], 1)
+                cur_ids, cur_sim = G.rows(batch)
+                ids = torch.cat([ids, cur_ids], 1)
+                sim = torch.cat([sim, cur_sim], 1)
                 # dedupe within rows: sort by id, blank repeated
                 so = torch.argsort(ids, dim=1, stable=True)
                 ids_s = torch.gather(ids, 1, so)
@@ -441,10 +532,8 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             dst = ids[keep]
             w = sim[keep]
             if replace:
-                G.adj[batch] = -1
-                G.sim[batch] = -float("inf")
-                G.deg[batch] = 0
-            G.add_links(xsel, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
+                G.clear_rows(batch)
+            G.add_links(xlink, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
             inserted[batch] = True
 
         pos = 0
@@ -466,13 +555,14 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
         finished.insert(0, G)
 
     # final assembly over all nodes (level 0 subset == everything)
-    graphs = [(f.sub.cpu().numpy(), f.adj.cpu().numpy()) for f in finished]
+    graphs = [(f.sub.cpu().numpy(), f.export()) for f in finished]
     all_ids = np.arange(n, dtype=np.int64)
     return _assemble_csr(lv_np, graphs, all_ids, d, mt, entry_global, M, ef_construction)
 
 
 @torch.no_grad()
-def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch") -> HnswCsr:
+def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch",
+                          linker: str = "torch") -> HnswCsr:
     """High-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3, p. 6): storage drops from ~2M links per node
     to ~m_low while the few hub nodes that most searches pass through keep their full lists.
 
@@ -484,9 +574,10 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
       * for every kept link v -> u the reverse link u -> v is offered as well and every node may hold up to 2M links in
         total, overflowing lists being shrunk with the same heuristic (paper: "all nodes establish bidirectional edges up
         to the maximum threshold M; only the number of outgoing selections of low-degree nodes is restricted").
-    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device; ``selector`` as
-    in build_graph_gpu."""
+    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device; ``selector`` and
+    ``linker`` as in build_graph_gpu."""
     _selector_fn(selector)
+    _check_linker(linker)
     n = g.ntotal
     if n == 0 or m_low >= 2 * M:
         return g
@@ -514,13 +605,13 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
     for b0 in range(0, src.shape[0], 1 << 20):
         a, b = x[src[b0 : b0 + (1 << 20)]].float(), x[dst[b0 : b0 + (1 << 20)]].float()
         w[b0 : b0 + (1 << 20)] = (a * b).sum(1) if mt == METRIC_INNER_PRODUCT else -((a - b) ** 2).sum(1)
-    G = _LevelGraph(torch.arange(n, device=dev), cap, selector)
-    xsel = _padded_table(x) if selector == "kernel" else x
+    G = _LevelGraph(torch.arange(n, device=dev), cap, selector, linker)
+    xsel = _padded_table(x) if selector == "kernel" or linker == "kernel" else x
     step = 1 << 21  # bound the temporaries of add_links
     for b0 in range(0, src.shape[0], step):
         s_, d_, w_ = src[b0 : b0 + step], dst[b0 : b0 + step], w[b0 : b0 + step]
         G.add_links(xsel, torch.cat([s_, d_]), torch.cat([d_, s_]), torch.cat([w_, w_]), mt)
-    new0 = G.adj.cpu().numpy()
+    new0 = G.export()
     # reassemble: level 0 replaced, upper levels copied
     nlev = g.levels.astype(np.int64)
     nptr = int(g.node_offsets[-1])
