@@ -420,6 +420,46 @@ int lm_pq_flat_search(lm_index *idx, int64_t n, const float *x, int32_t k, const
                       int64_t *labels, float *distances);
 int lm_pq_flat_search_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const lm_pq_search_params *params,
                              const uint32_t *d_allow, int64_t *d_labels, float *d_distances);
+/* Filtered PQ traversal: lm_pq_batch_search with an allow-list -- the filter applied INSIDE the DiskANN-style walk, as faiss and
+ * lm_index_search_filtered apply theirs: every evaluated node steers the search, only allowed nodes enter the result.  The reference filters
+ * AFTER the search (leann/api.py:785-790) and keeps the allowed among the L of the final list; lm_pq_flat_search ranks every allowed row but
+ * reads the whole code array per query tile.  (csrc/lm_pq_impl.h: k_pq_traverse<NTH, true>)
+ *   allow / d_allow   lm_exact_search's layout and rules: NULL = every node, else ceil(ntotal / 32) words, ONE bitmap for the whole call; bits at
+ *                     positions >= ntotal are ignored, whatever their value.  The host form takes a HOST array, uploaded per call into a buffer
+ *                     the index owns and grows (lm_index_search_filtered's); the device form borrows the caller's.
+ * Contract.
+ *   The walk.  It is exactly lm_pq_batch_search's with the same params: the lookup table, the entry point, the visited set, the W closest
+ *     unexpanded entries of the list of L = max(complexity, k), the stop rule.  The allow-list never influences the walk.
+ *   The evaluated set E(q): every node whose ADC distance the traversal computes -- the entry point and every fresh node of every hop.
+ *     |E(q)| is the query's share of ndis.
+ *   The allowed candidates F(q): the first L of E(q) n allowed under the key (adc, id) ascending -- NaN ranks as +inf, -0 as +0, ties go to
+ *     the lower id.
+ *   The tail: lm_pq_batch_search's, applied to F in place of the final list.  With use_deferred_fetch and a provider there is ONE provider
+ *     call per pass, for the sorted unique union of the F lists; otherwise the stored table is used if one is attached; otherwise -- or with
+ *     skip_search_reorder -- the PQ order stands.  Then the best k go out; empty slots get label -1 and +inf (L2) / -inf (ip).
+ *   Option "pq_rerank_expanded" has NO effect on this call: F is what gets ranked.
+ * Hence
+ *   1. with allow == NULL or a bitmap of all ones, labels and distance bits are those of lm_pq_batch_search at "pq_rerank_expanded" 0 (its
+ *      final list is the best L of E);
+ *   2. with any allow-list, ndis, nexpand and nrounds are those of lm_pq_batch_search; nunique is the number of rows requested for F;
+ *   3. a query's result does not depend on the other queries of the call, nor on how the call is cut into passes.
+ * A selective filter can still return FEWER than k hits: only nodes the walk evaluates can be returned (lm_pq_flat_search ranks every
+ * allowed row).  lm_index_get_option(idx, "filtered_allowed_evals", &v) reads, after this call too, the sum of |E(q) n allowed| over the
+ * queries; with allow == NULL it equals ndis.
+ * LDS rule.  The kernel keeps the lookup table, the walk's list and merge output, the hop's new keys and ids, the allowed-only list and FS
+ * staging keys in one workgroup's LDS.  FS = 64 for every (m, L, W, level-0 degree): a constant, so that the rule below is linear in L.  With
+ * new = max(W * max level-0 degree, 1) (the workspace's size; a graph with upper levels: at least their largest degree) and P(new) = new rounded up to a power of two, the call needs
+ *     1024 m + 24 L + 8 P(new) + 4 new + 8 FS  <=  161792 bytes (158 KiB)
+ * (lm_pq_batch_search: 1024 m + 16 L + 8 P(new) + 4 new).  At m = 96, W = 64, degree 64: L <= 576.
+ * Rejections come before anything is staged or launched, the outputs stay untouched: everything lm_pq_batch_search rejects, with the same
+ * codes (LM_EINVAL: NULL index / params / buffer, n < 0, k < 1, complexity < 1, recompute_neighbors != 0, beam_width > 64, more than 8192
+ * candidates per query into an exact rerank; LM_ESTATE: no codes attached, deferred fetch with neither a provider nor a table), and
+ * LM_EINVAL when the state does not fit the LDS by the rule above.  n == 0: LM_OK.  An empty index: every slot gets the empty values.
+ * All three workgroup widths of option "pq_threads" give the same bits. */
+int lm_pq_batch_search_filtered(lm_index *idx, int64_t n, const float *x, int32_t k, const lm_pq_search_params *params,
+                                const uint32_t *allow, int64_t *labels, float *distances);
+int lm_pq_batch_search_filtered_device(lm_index *idx, int64_t n, const float *d_x, int32_t k, const lm_pq_search_params *params,
+                                       const uint32_t *d_allow, int64_t *d_labels, float *d_distances);
 /* Index build time: the product quantiser that lm_pq_attach / lm_pq_attach_chunked take, made by the library -- nearest-centroid
  * assignment (lm_pq_encode) and Lloyd iterations over a sample (lm_pq_train); the role of DiskANN's generate_pq_pivots /
  * generate_pq_data_from_pivots behind diskann_backend.py:105-111 (leann_amd/pq.py holds the torch forms).

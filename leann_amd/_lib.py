@@ -116,6 +116,7 @@ EXPORTED_SYMBOLS = [
     "lm_index_search_filtered", "lm_index_search_filtered_device",
     "lm_pq_scan", "lm_pq_scan_workspace_bytes", "lm_pq_flat_search", "lm_pq_flat_search_device",
     "lm_pq_attach", "lm_pq_attach_chunked", "lm_pq_search_params_default", "lm_pq_batch_search", "lm_pq_batch_search_device",
+    "lm_pq_batch_search_filtered", "lm_pq_batch_search_filtered_device",
     "lm_add_layernorm_f16", "lm_attn_varlen_hd32_f16", "lm_attn_varlen_f16", "lm_embed_layernorm_f16", "lm_meanpool_varlen_f16",
     "lm_layer_tail_h384_f16", "lm_layer_tail_pack_h384", "lm_qkv_h384_f16", "lm_qkv_attn_h384_f16", "lm_h384_first_half_form", "lm_qkv_pack_h384", "lm_gemm_ws_h384_f16", "lm_gemm_f16", "lm_pack_tokens",
     "lm_tokens_create", "lm_tokens_free", "lm_tokens_gather", "lm_tokens_count",
@@ -192,6 +193,8 @@ def load() -> C.CDLL:
     lib.lm_pq_search_params_default.restype = None
     lib.lm_pq_batch_search.argtypes = [vp, i64, vp, i32, C.POINTER(PqSearchParams), vp, vp]
     lib.lm_pq_batch_search_device.argtypes = [vp, i64, vp, i32, C.POINTER(PqSearchParams), vp, vp]
+    lib.lm_pq_batch_search_filtered.argtypes = [vp, i64, vp, i32, C.POINTER(PqSearchParams), vp, vp, vp]
+    lib.lm_pq_batch_search_filtered_device.argtypes = [vp, i64, vp, i32, C.POINTER(PqSearchParams), vp, vp, vp]
     lib.lm_add_layernorm_f16.argtypes = [vp, vp, vp, vp, vp, i64, i32, C.c_float, vp]
     lib.lm_attn_varlen_hd32_f16.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.lm_attn_varlen_f16.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]

@@ -633,10 +633,18 @@ class Mi355xDiskannSearcher(Mi355xSearcher):
                zmq_port: Optional[int] = None, batch_recompute: bool = False, dedup_node_dis: bool = False,
                **kwargs) -> dict[str, Any]:
         """Same contract as DiskannSearcher.search (diskann_backend.py:383-471).  ``pq_flat=True`` / ``allowed_ids`` (keywords, default off): the
-        flat PQ scan of the allowed rows in place of the traversal, with the same rerank (Mi355xSearcher.search)."""
+        flat PQ scan of the allowed rows in place of the traversal, with the same rerank (Mi355xSearcher.search).  ``graph_filter=True`` /
+        ``allowed_ids`` (keywords, default off): the traversal itself with the allow-list applied inside the walk
+        (lm_pq_batch_search_filtered) -- the walk is the unfiltered one, the result the best allowed nodes among everything it evaluates; a
+        selective filter can still return fewer than ``top_k`` (``pq_flat=True`` ranks every allowed row).  Without ``allowed_ids`` it is the
+        plain traversal."""
         pq_flat, allowed_ids = bool(kwargs.get("pq_flat", False)), kwargs.get("allowed_ids")
-        if allowed_ids is not None and not pq_flat:
-            raise ValueError("allowed_ids needs pq_flat=True: the traversal kernel takes no filter")
+        graph_filter = bool(kwargs.get("graph_filter", False))
+        if pq_flat and graph_filter:
+            raise ValueError("pq_flat=True and graph_filter=True are different searches: choose one")
+        if allowed_ids is not None and not (pq_flat or graph_filter):
+            raise ValueError("allowed_ids needs pq_flat=True (a flat scan of the allowed rows) or graph_filter=True (the traversal with the "
+                             "allow-list applied inside the walk)")
         if recompute_embeddings and zmq_port is None:
             raise ValueError("zmq_port must be provided if recompute_embeddings is True")
         if pruning_strategy == "proportional":
@@ -669,6 +677,9 @@ class Mi355xDiskannSearcher(Mi355xSearcher):
                                     num_threads=int(self.num_threads), dedup_node_dis=bool(dedup_node_dis),
                                     prune_ratio=float(prune_ratio), batch_recompute=bool(batch_recompute),
                                     use_global_pruning=(pruning_strategy != "local"))
-        labels, distances = idx.pq_search(np.ascontiguousarray(query), int(top_k), params)
+        if graph_filter and allowed_ids is not None:
+            labels, distances = idx.pq_search_filtered(np.ascontiguousarray(query), int(top_k), params, allowed=allowed_ids)
+        else:
+            labels, distances = idx.pq_search(np.ascontiguousarray(query), int(top_k), params)
         string_labels = [[str(int(l)) for l in row] for row in labels]
         return {"labels": string_labels, "distances": distances}

@@ -31,16 +31,23 @@ struct PqArgs {
     int32_t exp_cap;  // > 0: the rerank set is EVERY expanded node (upstream DiskANN's full_retset), recorded in ws.pool (ws.ef = exp_cap
                       // entries per query); a query that expands more than exp_cap nodes falls back to its final list (counted)
     unsigned long long* n_exp_overflow;
+    // k_pq_traverse<NTH, true> only (lm_pq_batch_search_filtered):
+    const uint32_t* allow;          // ceil(N / 32) words, bit v = node v may enter the result; NULL = every node
+    int32_t FS;                     // staging keys of the allowed-only list (PQ_FILTER_STAGE)
+    unsigned long long* n_allowed;  // += the query's |E n allowed|
 };
 
 // dynamic LDS: lut[m*256] f32 | lpool[L] u64 | out[L] u64 | newk[Pmax] u64 | s_new[maxnew] i32
+//   FILTER:   lut[m*256] f32 | lpool[L] u64 | out[L] u64 | newk[Pmax] u64 | flist[L] u64 | fstage[FS] u64 | s_new[maxnew] i32
 // NTH = threads per workgroup = per query.  The lookup table alone is m x 1 KB of LDS (96 KB at m = 96): one workgroup per CU, so the
 // workgroup's own width is all the latency hiding the CU gets.  Round 2 ran 256 threads (ONE wave per SIMD; 2 % of the HBM rate); with
 // 1024 threads (four waves per SIMD) a hop's visited tests, code-row gathers, compactions and the bitonic sort all run four times wider.
 #ifndef PQ_RANK_SORT_MAX
 #define PQ_RANK_SORT_MAX 512  // survivors of a hop up to which their places in the list are counted instead of sorted (k_pq_traverse)
 #endif
-template <int NTH>
+// FILTER (lm_pq_batch_search_filtered): the SAME walk -- the allow-list steers nothing -- plus a second sorted list, flist, of the best L keys among the
+// evaluated nodes whose allow bit is set; flist, not the walk's list, is what the kernel leaves in ws.pool.  Every line of it sits behind `if constexpr`.
+template <int NTH, bool FILTER = false>
 __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev ws, PqArgs a) {
     constexpr int NWV = NTH / 64;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -48,11 +55,19 @@ __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev
     __shared__ uint64_t s_b[64];
     __shared__ int32_t s_pop[64];
     __shared__ int s_npop, s_wcnt[NWV];
+    __shared__ int s_fcnt[FILTER ? NWV : 1];  // (FILTER) a pass' keys for flist, per wave: written and read between the same two barriers as s_wcnt
     float* lut = (float*)smem;
     uint64_t* lpool = (uint64_t*)(lut + pq.m * 256);
     uint64_t* outp = lpool + a.L;
     uint64_t* newk = outp + a.L;
     int32_t* s_new = (int32_t*)(newk + a.Pmax);
+    uint64_t* flist = nullptr;
+    uint64_t* fstage = nullptr;
+    if constexpr (FILTER) {  // the two u64 arrays in front of the i32 one: maxnew may be odd
+        flist = newk + a.Pmax;
+        fstage = flist + a.L;
+        s_new = (int32_t*)(fstage + a.FS);
+    }
 
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* qv = a.Q + (size_t)q * a.Dp;
@@ -201,10 +216,16 @@ __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev
     };
     // ---- seed with the entry point (medoid) ----
     int npool = 0;
+    int nfl = 0, nallowed = 0;  // (FILTER) entries of flist (workgroup uniform); this lane's nodes that passed the allow test
+    if constexpr (FILTER) nfl = (!a.allow || ((a.allow[g.entry_point >> 5] >> (g.entry_point & 31)) & 1u)) ? 1 : 0;
     if (tid == 0) {
         const int32_t ep = g.entry_point;
         atomicOr(&vis[ep >> 5], 1u << (ep & 31));
         lpool[0] = make_key(adc1(ep), ep);
+        if constexpr (FILTER) {
+            if (nfl) flist[0] = lpool[0];
+            nallowed = nfl;
+        }
     }
     npool = 1;
     unsigned long long n_adc = 1;
@@ -303,20 +324,57 @@ __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev
         for (int i0 = 0; i0 < n; i0 += NTH) {
             const int i = i0 + tid;
             uint64_t key = KEY_NONE;
+            uint32_t aword = ~0u;  // (FILTER) the node's word of the allow-list, requested in front of its code row
+            int32_t vbit = 0;
             if (i < n) {
                 const int32_t v = s_new[i];
+                if constexpr (FILTER) {
+                    vbit = v & 31;
+                    if (a.allow) aword = a.allow[v >> 5];  // (a.allow: workgroup uniform)
+                }
                 key = make_key(adc1(v), v);
             }
             const bool keep = key < thr;  // KEY_NONE (idle lanes) is never below thr
             unsigned long long mk = __ballot(keep);
             if (lane == 0) s_wcnt[wv] = __popcll(mk);
+            // (FILTER) flist's own threshold: its last key once IT is full.  The walk's threshold must not be used: under a selective filter nearly every
+            // allowed key is worse than the walk's last entry and is still one of the best allowed ones.
+            bool fkeep = false;
+            unsigned long long fmk = 0;
+            if constexpr (FILTER) {
+                const bool allowed = i < n && ((aword >> vbit) & 1u);
+                nallowed += allowed ? 1 : 0;
+                fkeep = allowed && key < (nfl >= a.L ? flist[a.L - 1] : KEY_NONE);
+                fmk = __ballot(fkeep);
+                if (lane == 0) s_fcnt[wv] = __popcll(fmk);
+            }
             __syncthreads();
             int woff = 0;
             for (int w2 = 0; w2 < wv; ++w2) woff += s_wcnt[w2];
             if (keep) newk[kept + woff + __popcll(mk & ((1ull << lane) - 1ull))] = key;
 #pragma unroll
             for (int w2 = 0; w2 < NWV; ++w2) kept += s_wcnt[w2];
+            int fcnt = 0, frank = 0;
+            if constexpr (FILTER) {
+                for (int w2 = 0; w2 < wv; ++w2) frank += s_fcnt[w2];
+                frank += __popcll(fmk & ((1ull << lane) - 1ull));
+#pragma unroll
+                for (int w2 = 0; w2 < NWV; ++w2) fcnt += s_fcnt[w2];
+            }
             __syncthreads();
+            if constexpr (FILTER) {
+                // the pass' keys for flist, FS at a time through the staging area: placed by counting, merged into outp (free until the hop's own merge below),
+                // copied back.  fcnt comes from s_fcnt: every lane runs the same number of rounds, each with three barriers (staged, merged, copied back).  In steady state fcnt is 0 or a few.
+                for (int base = 0; base < fcnt; base += a.FS) {
+                    const int cnt = min(a.FS, fcnt - base);
+                    if (fkeep && frank >= base && frank < base + cnt) fstage[frank - base] = key;
+                    __syncthreads();
+                    rank_merge_unsorted<NTH>(flist, nfl, fstage, cnt, outp, a.L, tid);
+                    nfl = min(a.L, nfl + cnt);
+                    for (int t = tid; t < nfl; t += NTH) flist[t] = outp[t];
+                    __syncthreads();
+                }
+            }
         }
         if (kept > 0 && kept <= counting_merge_limit(PQ_RANK_SORT_MAX)) {  // (round 6) few survivors -- the steady state: their places by counting, one barrier (lm_beam_common.h)
             rank_merge_unsorted<NTH>(lpool, npool, newk, kept, outp, a.L, tid);
@@ -338,7 +396,18 @@ __global__ __launch_bounds__(NTH) void k_pq_traverse(GraphDev g, PqDev pq, WsDev
     // ---- rerank set -> global pool: the final candidate list, or (exp_cap > 0) the expanded nodes already recorded there ----
     uint64_t* pool = ws.pool + (size_t)q * ws.ef;
     const bool expanded_set = a.exp_cap > 0 && nexp <= a.exp_cap;
-    if (!expanded_set)
+    if constexpr (FILTER) {  // flist in place of the walk's list (exp_cap is 0 for this call); the lanes' allow-test passes -> one sum per query
+        for (int m2 = 32; m2 >= 1; m2 >>= 1) nallowed += __shfl_xor(nallowed, m2);
+        if (lane == 0) s_fcnt[wv] = nallowed;
+        __syncthreads();  // (the barrier that ended the walk's last hop has been passed by every lane: s_fcnt is free)
+        for (int i = tid; i < nfl; i += NTH) pool[i] = flist[i];
+        npool = nfl;
+        if (tid == 0) {
+            unsigned long long tot = 0;
+            for (int w2 = 0; w2 < NWV; ++w2) tot += (unsigned long long)s_fcnt[w2];
+            atomicAdd(a.n_allowed, tot);
+        }
+    } else if (!expanded_set)
         for (int i = tid; i < npool; i += NTH) pool[i] = lpool[i];
     if (tid == 0) {
         if (a.exp_cap > 0 && !expanded_set) atomicAdd(a.n_exp_overflow, 1ull);
@@ -496,8 +565,32 @@ static int pq_rerank_tail(lm_index* ix, int32_t B, const float* d_q, int32_t k, 
     return LM_OK;
 }
 
+// lm_pq_batch_search_filtered: the allow-list of the call (NULL = every node)
+struct PqFilterPass {
+    const uint32_t* d_allow;
+};
+#define PQ_FILTER_STAGE 64  // FS: staging keys of the filtered traversal's allowed-only list -- the same for every (m, L, W, degree); see the header's LDS rule
+#define PQ_LDS_LIMIT (158 * 1024)  // 160 KiB per workgroup minus the kernel's static LDS (about 1.2 KiB)
+
+// dynamic LDS of k_pq_traverse: table | list | merge output | new keys | new ids, + (filtered) allowed-only list | staging
+static size_t pq_traverse_lds(int32_t m, int32_t L, int32_t maxnew, bool filtered) {
+    return (size_t)m * 256 * 4 + (size_t)2 * L * 8 + (size_t)next_pow2(maxnew) * 8 + (size_t)maxnew * 4 + (filtered ? (size_t)8 * L + (size_t)8 * PQ_FILTER_STAGE : 0);
+}
+
+template <int NTH>
+static int launch_pq_traverse(bool filtered, int32_t B, size_t shmem, hipStream_t st, const GraphDev& g, const PqDev& pq, const WsDev& ws, const PqArgs& pa) {
+    if (filtered) {
+        LM_HIP(hipFuncSetAttribute((const void*)k_pq_traverse<NTH, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        hipLaunchKernelGGL((k_pq_traverse<NTH, true>), dim3(B), dim3(NTH), shmem, st, g, pq, ws, pa);
+    } else {
+        LM_HIP(hipFuncSetAttribute((const void*)k_pq_traverse<NTH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+        hipLaunchKernelGGL(k_pq_traverse<NTH>, dim3(B), dim3(NTH), shmem, st, g, pq, ws, pa);
+    }
+    return LM_OK;
+}
+
 static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, const lm_pq_search_params& prm,
-                          float* d_dist, int64_t* d_labels) {
+                          float* d_dist, int64_t* d_labels, const PqFilterPass* flt = nullptr) {
     const int32_t L = std::max(prm.complexity, k);
     const int32_t W = std::max(prm.beam_width, 1);
     if (W > 64) LM_FAIL(LM_EINVAL, "beam_width > 64 is not supported by the PQ traversal kernel");
@@ -506,7 +599,8 @@ static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, 
     // The record replaces the candidate list as what the traversal leaves in ws.pool (keys in expansion order, distance 0), so it is kept
     // ONLY when an exact rerank follows: with skip_search_reorder, or with neither a table nor a provider, the PQ-ordered list is the result.
     const bool rerank = !prm.skip_search_reorder && ((prm.use_deferred_fetch && ix->provider) || ix->d_table != nullptr);
-    const int32_t exp_cap = (ix->pq_rerank_expanded && rerank) ? std::min<int32_t>(8192, 4 * L) : 0;
+    // (the filtered call ranks its allowed-only list: the option has no effect on it)
+    const int32_t exp_cap = (ix->pq_rerank_expanded && rerank && !flt) ? std::min<int32_t>(8192, 4 * L) : 0;
     if (exp_cap && L > 8192) LM_FAIL(LM_EINVAL, "pq_rerank_expanded: complexity <= 8192");
     int rc = ensure_ws(ix, B, exp_cap ? exp_cap : L, W);
     if (rc) return rc;
@@ -530,25 +624,29 @@ static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, 
     pa.n_adc_q = ix->d_pq_nadc; pa.rounds_q = ix->d_pq_rounds;
     pa.exp_cap = exp_cap;
     pa.n_exp_overflow = ws.counters + C_PQ_OVERFLOW;
-    size_t shmem = (size_t)ix->pq_m * 256 * 4 + (size_t)2 * L * 8 + (size_t)pa.Pmax * 8 + (size_t)ws.maxnew * 4;
-    if (shmem > 158 * 1024)  // 160 KiB per workgroup minus the kernel's ~1.1 KiB of static LDS
+    pa.allow = flt ? flt->d_allow : nullptr;
+    pa.FS = PQ_FILTER_STAGE;
+    pa.n_allowed = ws.counters + C_PQ_ALLOWED;
+    const size_t shmem = pq_traverse_lds(ix->pq_m, L, ws.maxnew, flt != nullptr);
+    if (shmem > PQ_LDS_LIMIT)
         LM_FAIL(LM_EINVAL, "PQ search state does not fit the 160 KB LDS (reduce m, complexity or beam_width)");
-    if (ix->pq_threads == 256) LM_HIP(hipFuncSetAttribute((const void*)k_pq_traverse<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    else if (ix->pq_threads == 512) LM_HIP(hipFuncSetAttribute((const void*)k_pq_traverse<512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    else LM_HIP(hipFuncSetAttribute((const void*)k_pq_traverse<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     LM_HIP(hipMemsetAsync(ws.visited, 0, (size_t)B * ws.nw * 4, st));
     LM_HIP(hipMemsetAsync(ws.counters, 0, C_NCOUNTERS * sizeof(unsigned long long), st));
     {
         EvScope es(ix, &ix->ev_update);
         // option "pq_threads" (256 / 512 / 1024; default 1024): workgroup width of the traversal (A/B; identical results)
-        if (ix->pq_threads == 256) hipLaunchKernelGGL(k_pq_traverse<256>, dim3(B), dim3(256), shmem, st, g, pq, ws, pa);
-        else if (ix->pq_threads == 512) hipLaunchKernelGGL(k_pq_traverse<512>, dim3(B), dim3(512), shmem, st, g, pq, ws, pa);
-        else hipLaunchKernelGGL(k_pq_traverse<1024>, dim3(B), dim3(1024), shmem, st, g, pq, ws, pa);
+        int lrc;
+        if (ix->pq_threads == 256) lrc = launch_pq_traverse<256>(flt != nullptr, B, shmem, st, g, pq, ws, pa);
+        else if (ix->pq_threads == 512) lrc = launch_pq_traverse<512>(flt != nullptr, B, shmem, st, g, pq, ws, pa);
+        else lrc = launch_pq_traverse<1024>(flt != nullptr, B, shmem, st, g, pq, ws, pa);
+        if (lrc) return lrc;
     }
     LM_HIP(hipGetLastError());
     ix->stats.update_launches++;
     hipLaunchKernelGGL(k_pq_stats, dim3(1), dim3(256), 0, st, ws, pa);
-    return pq_rerank_tail(ix, B, d_q, k, prm, rerank, exp_cap ? exp_cap : L, d_dist, d_labels);
+    rc = pq_rerank_tail(ix, B, d_q, k, prm, rerank, exp_cap ? exp_cap : L, d_dist, d_labels);
+    if (!rc && flt) ix->filtered_allowed_evals += (int64_t)ix->h_counters[C_PQ_ALLOWED];  // (the tail has copied the pass' counters and waited for them)
+    return rc;
 }
 
 extern "C" {
@@ -598,7 +696,7 @@ void lm_pq_search_params_default(lm_pq_search_params* p) {
 }
 
 static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const lm_pq_search_params* params,
-                            int64_t* d_labels, float* d_dist) {
+                            int64_t* d_labels, float* d_dist, const PqFilterPass* flt = nullptr) {
     if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
     if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
     if (params->recompute_neighbors)
@@ -608,6 +706,7 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
         LM_FAIL(LM_ESTATE, "deferred fetch requested but neither an embedding provider nor stored embeddings are attached");
     LM_HIP(hipSetDevice(ix->device));
     ix->stats = lm_search_stats{};
+    if (flt) ix->filtered_allowed_evals = 0;
     if (n == 0) return LM_OK;
     hipStream_t st = ix->stream;
     if (ix->N == 0 || ix->entry_point < 0) {
@@ -634,7 +733,7 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     maxb = std::max<int64_t>(1, std::min<int64_t>(maxb, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));
     for (int64_t off = 0; off < n; off += maxb) {
         int32_t B = (int32_t)std::min<int64_t>(maxb, n - off);
-        int rc = pq_search_pass(ix, B, d_q + (size_t)off * ix->Dp, k, *params, d_dist + (size_t)off * k, d_labels + (size_t)off * k);
+        int rc = pq_search_pass(ix, B, d_q + (size_t)off * ix->Dp, k, *params, d_dist + (size_t)off * k, d_labels + (size_t)off * k, flt);
         if (rc) return rc;
     }
     LM_HIP(hipStreamSynchronize(st));
@@ -642,6 +741,65 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
         ix->stats.update_ms = drain_events(ix, ix->ev_update);
         ix->stats.provider_ms = drain_events(ix, ix->ev_provider);
     }
+    return LM_OK;
+}
+
+// Everything lm_pq_batch_search_filtered* rejects, in front of any staging or launch: pq_search_device's argument and state checks (it repeats them), then
+// what pq_search_pass and the rerank tail would refuse after their first launches -- the beam width, the LDS rule of the filtered kernel, the rerank sort.
+static int pq_filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm_pq_search_params* params) {
+    if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
+    if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
+    if (params->recompute_neighbors)
+        LM_FAIL(LM_EINVAL, "recompute_neighbors != 0 is not supported: the traversal runs on PQ distances only, as the reference runs it (diskann_backend.py:444-451)");
+    if (!ix->d_pq_codes) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
+    if (params->use_deferred_fetch && !ix->provider && !ix->d_table)
+        LM_FAIL(LM_ESTATE, "deferred fetch requested but neither an embedding provider nor stored embeddings are attached");
+    if (n == 0 || ix->N == 0 || ix->entry_point < 0) return LM_OK;
+    const int32_t L = std::max(params->complexity, k), W = std::max(params->beam_width, 1);
+    if (W > 64) LM_FAIL(LM_EINVAL, "beam_width > 64 is not supported by the PQ traversal kernel");
+    const int32_t maxnew = std::max({W * ix->maxdeg0, ix->maxdeg_up, 1});  // ensure_ws's
+    if (pq_traverse_lds(ix->pq_m, L, maxnew, true) > PQ_LDS_LIMIT)
+        LM_FAIL(LM_EINVAL, "filtered PQ search state does not fit the 160 KB LDS: m*1024 + 24*L + 8*P(W*degree) + 4*W*degree + 512 bytes must be at most 161792 "
+                           "(reduce complexity or beam_width)");
+    const bool rerank = !params->skip_search_reorder && ((params->use_deferred_fetch && ix->provider) || ix->d_table != nullptr);
+    if (rerank && (size_t)next_pow2(L) * 8 > 64 * 1024) LM_FAIL(LM_EINVAL, "complexity too large for the rerank kernel (<= 8192 candidates per query)");
+    return LM_OK;
+}
+
+int lm_pq_batch_search_filtered_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const lm_pq_search_params* params, const uint32_t* d_allow,
+                                       int64_t* d_labels, float* d_distances) {
+    if (int rc = pq_filtered_checks(ix, n, k, params)) return rc;
+    if (n > 0 && (!d_x || !d_labels || !d_distances)) LM_FAIL(LM_EINVAL, "NULL buffer");
+    const PqFilterPass flt{d_allow};
+    return pq_search_device(ix, n, d_x, k, params, d_labels, d_distances, &flt);
+}
+
+int lm_pq_batch_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t k, const lm_pq_search_params* params, const uint32_t* allow, int64_t* labels,
+                                float* distances) {
+    if (int rc = pq_filtered_checks(ix, n, k, params)) return rc;
+    PqFilterPass flt{nullptr};
+    if (n == 0) return pq_search_device(ix, 0, nullptr, k, params, nullptr, nullptr, &flt);  // the stats of an empty call
+    if (!x || !labels || !distances) LM_FAIL(LM_EINVAL, "NULL buffer");
+    LM_HIP(hipSetDevice(ix->device));
+    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
+    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
+    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
+    if (allow) {  // (lm_index_search_filtered's buffer: one allow-list per call, whichever graph search it is for)
+        if (allow_bytes > ix->filter_allow_bytes) {
+            if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
+            ix->d_filter_allow = nullptr;
+            ix->filter_allow_bytes = 0;
+            LM_HIP(hipMalloc((void**)&ix->d_filter_allow, std::max<size_t>(allow_bytes, 16)));
+            ix->filter_allow_bytes = std::max<size_t>(allow_bytes, 16);
+        }
+        flt.d_allow = ix->d_filter_allow;
+        if (allow_bytes) LM_HIP(hipMemcpyAsync(ix->d_filter_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
+    }
+    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
+    if (int rc = pq_search_device(ix, n, ix->d_stage_x, k, params, ix->d_stage_l, ix->d_stage_d, &flt)) return rc;
+    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipStreamSynchronize(ix->stream));
     return LM_OK;
 }
 

@@ -383,6 +383,47 @@ class Mi355xIndex:
         self._raise_provider(rc, "lm_pq_flat_search_device")
         return labels, dist
 
+    # ---- the PQ traversal with an allow-list ---------------------------------------------------------
+    def pq_search_filtered(self, queries: np.ndarray, k: int, params: PqSearchParams, allowed=None):
+        """:meth:`pq_search` with an allow-list applied inside the walk (lm_pq_batch_search_filtered): the walk is the unfiltered one, the result
+        the best of the ALLOWED nodes among everything it evaluates, re-ranked as :meth:`pq_search` re-ranks its list -> (labels, distances)
+        numpy, slots without a node -1 / +-inf.  ``allowed``: None, a bool mask [ntotal] or an array of node ids."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim != 2 or q.shape[1] != self.info.d:
+            raise ValueError(f"query must be (B, {self.info.d}) float32")
+        n = q.shape[0]
+        dist = np.empty((n, k), dtype=np.float32)
+        labels = np.empty((n, k), dtype=np.int64)
+        words = None if allowed is None else allow_bitmap(allowed, int(self.info.ntotal))
+        rc = self._lib.lm_pq_batch_search_filtered(self._h, n, _np_ptr(q), k, C.byref(params), None if words is None else _np_ptr(words),
+                                                   _np_ptr(labels), _np_ptr(dist))
+        self._raise_provider(rc, "lm_pq_batch_search_filtered")
+        return labels, dist
+
+    def pq_search_filtered_device(self, queries, k: int, params: PqSearchParams, allowed=None):
+        """The same with ``queries`` a CUDA/HIP torch tensor (B, D) f32; returns torch tensors.  ``allowed`` as for :meth:`pq_search_filtered`, or
+        a device int32 tensor that already holds the bitmap words."""
+        import torch
+
+        assert queries.is_cuda and queries.dtype == torch.float32 and queries.is_contiguous()
+        n = queries.shape[0]
+        dist = torch.empty((n, k), dtype=torch.float32, device=queries.device)
+        labels = torch.empty((n, k), dtype=torch.int64, device=queries.device)
+        words = None
+        if allowed is not None:
+            if isinstance(allowed, torch.Tensor) and allowed.is_cuda and allowed.dtype == torch.int32:
+                words = allowed.contiguous()
+                if words.numel() != (int(self.info.ntotal) + 31) // 32:
+                    raise ValueError("a device bitmap must hold ceil(ntotal / 32) int32 words")
+            else:
+                host = allowed.cpu().numpy() if isinstance(allowed, torch.Tensor) else allowed
+                words = torch.from_numpy(allow_bitmap(host, int(self.info.ntotal)).view(np.int32)).to(queries.device)
+        rc = self._lib.lm_pq_batch_search_filtered_device(self._h, n, C.c_void_p(queries.data_ptr()), k, C.byref(params),
+                                                          None if words is None else C.c_void_p(words.data_ptr()), C.c_void_p(labels.data_ptr()),
+                                                          C.c_void_p(dist.data_ptr()))
+        self._raise_provider(rc, "lm_pq_batch_search_filtered_device")
+        return labels, dist
+
     def stats(self) -> dict:
         st = SearchStats()
         check(self._lib.lm_index_get_stats(self._h, C.byref(st)))
