@@ -62,6 +62,48 @@ int lm_index_create_from_csr(int64_t ntotal, int32_t d, int32_t metric,
                              const int32_t *neighbors, int64_t n_neighbors,
                              const int32_t *levels /* ntotal */,
                              int32_t entry_point, int32_t max_level, int device, lm_index **out);
+
+/* An index that is a live VIEW of device-resident level adjacencies: the graph a caller is building with lm_select_neighbors and
+ * lm_graph_add_links, searched in place.  The handle holds no copy of the graph.  (csrc/lm_view_impl.h)
+ *   levels   HOST array of n_levels descriptors, levels[l] = level l; the device arrays they point to are BORROWED: the caller keeps
+ *            them alive (and at the same addresses) for as long as the handle is searched.
+ * Graph.  The neighbours of node v at level l are the non-empty slots of v's row in levels[l].d_adj, in slot order; the row index is
+ * v's position in levels[l].d_nodes, found by binary search.  A node that level l does not list has no neighbours there and is never
+ * dereferenced.  Level 0 must be the identity level (d_nodes == NULL, n_rows == ntotal).  max_level = n_levels - 1.
+ * That d_nodes is strictly ascending is the caller's promise: it is NOT checked (the array lives on the device; checking it would
+ * need a device read).  A list that is not sorted makes nodes unfindable, nothing worse: only rows below n_rows are read.
+ * Live.  A search reads the arrays as they are when its kernel runs, in stream order: after lm_graph_add_links (or any other writer)
+ * on the index's stream (lm_index_set_stream), the next search sees the new lists.  The handle is not re-created for this.
+ * Equivalence.  With recompute = 0 and an attached table (lm_index_attach_table, either location, fp32 or fp16), lm_index_search* on
+ * the view returns what lm_index_search* returns on the CSR index in which node v carries levels 0 .. top(v) -- top(v) = the highest
+ * level that lists v -- and each list holds the non-empty slots of v's row in slot order: labels, distance bits, ndis, nexpand and
+ * nrounds are identical, for any efSearch, beam_size, check_relative_distance, k and max_batch; hence also identical to
+ * oracle/lm_oracle.c:orc_search on that CSR.  A query's result does not depend on the other queries of the call nor on how max_batch
+ * cuts the call into passes.
+ * lm_index_info: max_degree0 = levels[0].cap, max_degree_up = the largest upper cap, n_neighbors = the sum of n_rows * cap (slots,
+ * not links); the other fields keep their meaning.
+ * What a view does not serve -- each returns LM_ESTATE before anything is staged or launched, the outputs untouched: a search with
+ * recompute = 1, batch_size > 0 or pq_pruning_ratio > 0; a search while option "persistent_table" is 0 (a view has the persistent
+ * launch only) or without a table; lm_index_search_filtered*; lm_pq_attach*, lm_pq_batch_search*, lm_pq_flat_search* on the handle;
+ * lm_index_set_hub_cache.  lm_index_search_exact* reads only the table and keeps working.
+ * LDS rule: with maxnew = max(beam_size * levels[0].cap, largest upper cap, 1) and P(x) = the next power of two, a search needs
+ * (2 * max(efSearch, k) + P(maxnew)) * 8 + 4 * maxnew <= 150 KiB (the persistent launch's own rule with the capacity in place of the
+ * largest degree); otherwise LM_EINVAL, the outputs untouched -- a view has no lock-step fallback.  beam_size > 64: LM_EINVAL.
+ * Option "persistent_wave": -1 (auto) and 0 give the 256-thread workgroup per query (a view knows no mean degree), 1 the wave per
+ * query; both give the same bits.
+ * LM_EINVAL at creation, no handle returned: NULL levels or out; n_levels < 1; ntotal < 0 or > INT32_MAX; an unsupported d (the
+ * widths the search kernels cover: d padded to 64..384, 512, 768, 1024) or metric; a level with cap < 1, n_rows < 0 or
+ * n_rows > ntotal; level 0 not the identity level; an upper level with n_rows > 0 and NULL d_nodes (unless n_rows == ntotal: the
+ * identity); NULL d_adj with n_rows > 0; entry_point outside [0, ntotal) when ntotal > 0.  ntotal == 0 gives a valid handle whose
+ * searches fill the empty values.  lm_index_free frees the handle, never the level arrays. */
+typedef struct {
+    const int32_t *d_nodes; /* n_rows node ids, strictly ascending; NULL = identity (row r is node r), then n_rows == ntotal */
+    const int32_t *d_adj;   /* [n_rows][cap], lm_graph_add_links' layout: a slot value outside [0, ntotal) is EMPTY, holes tolerated */
+    int64_t n_rows;
+    int32_t cap;
+} lm_graph_level;
+int lm_index_create_view(int64_t ntotal, int32_t d, int32_t metric, const lm_graph_level *levels /* host array */,
+                         int32_t n_levels, int32_t entry_point, int device, lm_index **out);
 void lm_index_free(lm_index *idx);
 
 typedef struct {

@@ -37,6 +37,10 @@ class IndexInfo(C.Structure):
     ]
 
 
+class GraphLevel(C.Structure):  # include/leann_mi355x.h: lm_graph_level
+    _fields_ = [("d_nodes", C.c_void_p), ("d_adj", C.c_void_p), ("n_rows", C.c_int64), ("cap", C.c_int32)]
+
+
 class SearchParams(C.Structure):
     """Mirror of lm_search_params == faiss.SearchParametersHNSW as filled in hnsw_backend.py:203-234."""
 
@@ -107,7 +111,7 @@ PROVIDER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(
 # every symbol include/leann_mi355x.h declares (checked by tests/test_abi.py)
 EXPORTED_SYMBOLS = [
     "lm_last_error", "lm_device_count", "lm_version", "lm_abi_revision",
-    "lm_index_read", "lm_index_create_from_csr", "lm_index_free", "lm_index_info",
+    "lm_index_read", "lm_index_create_from_csr", "lm_index_create_view", "lm_index_free", "lm_index_info",
     "lm_index_attach_table", "lm_index_set_provider", "lm_index_set_hub_cache", "lm_index_set_stream",
     "lm_search_params_default", "lm_index_search", "lm_index_search_device",
     "lm_index_get_stats", "lm_index_set_profiling", "lm_index_set_option", "lm_index_get_option", "lm_index_event_overhead_us",
@@ -149,6 +153,7 @@ def load() -> C.CDLL:
     lib.lm_device_count.restype = C.c_int
     lib.lm_index_read.argtypes = [C.c_char_p, C.c_int, C.POINTER(vp)]
     lib.lm_index_create_from_csr.argtypes = [i64, i32, i32, vp, vp, i64, vp, i64, vp, i32, i32, C.c_int, C.POINTER(vp)]
+    lib.lm_index_create_view.argtypes = [i64, i32, i32, C.POINTER(GraphLevel), i32, i32, C.c_int, C.POINTER(vp)]
     lib.lm_index_free.argtypes = [vp]
     lib.lm_index_free.restype = None
     lib.lm_index_info.argtypes = [vp, C.POINTER(IndexInfo)]

@@ -139,7 +139,10 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         ``hub_preserving_m`` > 0 additionally applies the paper's high-degree-preserving pruning (Algorithm 3): ~m links per
         node, full lists for the 2 % hub nodes -- the storage side of a recompute (pruned) index.  ``gpu_select_kernel`` (bool, default
         False): both of these pick neighbours with the library's kernel (lm_select_neighbors) instead of torch ops.  ``gpu_link_kernel``
-        (bool, default False): both of these insert their links with the library's kernel (lm_graph_add_links) instead of torch ops."""
+        (bool, default False): both of these insert their links with the library's kernel (lm_graph_add_links) instead of torch ops.
+        ``gpu_search_view`` (bool, default False): the GPU builder searches its level graphs in place through a view index
+        (lm_index_create_view, build_graph_gpu(search="view")) instead of re-assembling a CSR for every insert batch; needs
+        ``gpu_link_kernel``."""
         from .hnsw_builder import build_hnsw
 
         bp = self.build_params
@@ -147,6 +150,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         m_low = int(bp.get("hub_preserving_m", 0) or 0)
         selector = "kernel" if bool(bp.get("gpu_select_kernel", False)) else "torch"
         linker = "kernel" if bool(bp.get("gpu_link_kernel", False)) else "torch"
+        search = "view" if bool(bp.get("gpu_search_view", False)) else "csr"
         use_gpu = data.shape[0] >= thr and _lib.device_count() > 0
         if not use_gpu and m_low <= 0:
             return build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
@@ -156,7 +160,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
 
         if use_gpu:
             x = torch.from_numpy(np.ascontiguousarray(data)).to(torch.device("cuda", int(bp.get("device", 0))))
-            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker)
+            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker, search=search)
         else:
             x = torch.from_numpy(np.ascontiguousarray(data))
             if selector == "kernel" or linker == "kernel":  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)

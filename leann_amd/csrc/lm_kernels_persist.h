@@ -27,8 +27,12 @@ struct PersistArgs {
 // (Round 6 measured a five-waves-per-SIMD register allocation of this kernel -- __launch_bounds__(NT, 5): 96 VGPRs and 20-52 B of scratch instead of the
 // compiler's 112-114 VGPRs = four waves -- against it: slower at every batch size and beam, 4.75-5.03 vs 5.08 TB/s at 8192 queries, 6.21 vs 6.50 at 32768
 // (profiles/r6_table_mode_queries_in_flight_and_occupancy_sweep.json).  What raises the rate is queries in flight: 5.1 / 6.0 / 6.5 TB/s at 8192 / 16384 / 32768.)
-template <int NCH, bool L2, bool F16, int NT>
-__global__ __launch_bounds__(NT) void k_search_table(GraphDev g, WsDev ws, PersistArgs a) {
+// GA = the graph accessor: GraphDev (the compact CSR) or ViewDev (lm_view_impl.h: fixed-capacity level adjacencies read in place, empty
+// slots skipped).  The two differ in how a new-list is gathered -- the upper-level step and the level-0 hop below --; everything after the
+// new-list is shared, and the CSR instantiations compile to the instruction stream they had before the accessor became a parameter.
+template <int NCH, bool L2, bool F16, int NT, class GA = GraphDev>
+__global__ __launch_bounds__(NT) void k_search_table(GA g, WsDev ws, PersistArgs a) {
+    constexpr bool VIEW = graph_is_view<GA>::value;
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ uint32_t s_off[65];
     __shared__ uint64_t s_b[64];
@@ -80,10 +84,14 @@ __global__ __launch_bounds__(NT) void k_search_table(GraphDev g, WsDev ws, Persi
     rounds = 1;
     // ---- upper levels: greedy descent (faiss greedy_update_nearest) ----
     for (int level = a.max_level; level > 0;) {
-        uint64_t b;
         uint32_t cnt;
-        nbr_range(g, key_id(cur), level, b, cnt);
-        for (uint32_t j = tid; j < cnt; j += NT) s_new[j] = g.neighbors[b + j];
+        if constexpr (VIEW) {
+            cnt = (uint32_t)view_upper_list<NT>(g, key_id(cur), level, s_new, s_wcnt, tid);
+        } else {
+            uint64_t b;
+            nbr_range(g, key_id(cur), level, b, cnt);
+            for (uint32_t j = tid; j < cnt; j += NT) s_new[j] = g.neighbors[b + j];
+        }
         if (tid == 0) s_best = KEY_NONE;
         __syncthreads();
         eval_new((int)cnt);
@@ -108,35 +116,51 @@ __global__ __launch_bounds__(NT) void k_search_table(GraphDev g, WsDev ws, Persi
         if (tid < 64) {
             const int found = select_pops(lpool, npool, ws.W, a.check_rel, ws.efs, nsteps, s_pop, tid);
             LM_WAVE_SYNC();  // s_pop[r] written by the popping lanes, read below by lane r
-            uint32_t cnt = 0;
-            if (tid < found) {
-                L0Range r = g.l0[s_pop[tid]];
-                s_b[tid] = r.begin;
-                cnt = r.count;
+            if constexpr (VIEW) {  // every pop contributes cap0 slots: no ranges, no scan
+                if (tid == 0) s_npop = found;
+            } else {
+                uint32_t cnt = 0;
+                if (tid < found) {
+                    L0Range r = g.l0[s_pop[tid]];
+                    s_b[tid] = r.begin;
+                    cnt = r.count;
+                }
+                uint32_t x = cnt;
+                for (int d = 1; d < 64; d <<= 1) {
+                    uint32_t y = __shfl_up(x, d);
+                    if (tid >= d) x += y;
+                }
+                if (tid == 0) {
+                    s_off[0] = 0;
+                    s_npop = found;
+                }
+                if (tid < found) s_off[tid + 1] = x;
             }
-            uint32_t x = cnt;
-            for (int d = 1; d < 64; d <<= 1) {
-                uint32_t y = __shfl_up(x, d);
-                if (tid >= d) x += y;
-            }
-            if (tid == 0) {
-                s_off[0] = 0;
-                s_npop = found;
-            }
-            if (tid < found) s_off[tid + 1] = x;
         }
         __syncthreads();
         const int np = s_npop;
         if (np == 0) break;
         nsteps += np;
         rounds++;
-        const uint32_t totalc = s_off[np];
+        uint32_t totalc;
+        if constexpr (VIEW) totalc = (uint32_t)np * (uint32_t)g.cap0;
+        else totalc = s_off[np];
         int total = 0;
         for (uint32_t f0 = 0; f0 < totalc; f0 += NT) {
             const uint32_t f = f0 + tid;
             bool fresh = false;
             int32_t v = -1;
-            if (f < totalc) {
+            if constexpr (VIEW) {
+                if (f < totalc) {
+                    const uint32_t r = f / (uint32_t)g.cap0;  // slot f belongs to pop f / cap0
+                    v = g.adj0[(int64_t)s_pop[r] * g.cap0 + (f - r * (uint32_t)g.cap0)];
+                    if (view_id_ok(v, g.N)) {  // an empty slot is not fresh and never reaches the visited bitmap
+                        uint32_t bit = 1u << (v & 31);
+                        uint32_t old = atomicOr(&vis[v >> 5], bit);
+                        fresh = !(old & bit);
+                    }
+                }
+            } else if (f < totalc) {
                 int lo = 0, hi = np - 1;
                 while (lo < hi) {
                     int mid = (lo + hi + 1) >> 1;

@@ -493,6 +493,7 @@ static int pq_flat_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, 
 }
 
 static int pq_flat_index_checks(lm_index* ix, int64_t n, int32_t k, const lm_pq_search_params* params) {
+    LM_NOT_ON_VIEW(ix, "lm_pq_flat_search");
     if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
     if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
     if (params->recompute_neighbors) LM_FAIL(LM_EINVAL, "recompute_neighbors != 0 is not supported (as in lm_pq_batch_search)");

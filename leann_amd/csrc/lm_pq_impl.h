@@ -653,6 +653,7 @@ extern "C" {
 
 int lm_pq_attach_chunked(lm_index* ix, int32_t m, const int32_t* chunk_offsets, const float* codebooks, const uint8_t* codes, int64_t ntotal) {
     if (!ix || !chunk_offsets || !codebooks || !codes) LM_FAIL(LM_EINVAL, "NULL argument");
+    LM_NOT_ON_VIEW(ix, "lm_pq_attach_chunked");
     if (ntotal != ix->N) LM_FAIL(LM_EINVAL, "code count does not match the index");
     if (m <= 0 || m % 4 || m > 4096) LM_FAIL(LM_EINVAL, "m must be a positive multiple of 4 (pad the codes with empty chunks)");
     if (chunk_offsets[0] != 0) LM_FAIL(LM_EINVAL, "chunk_offsets[0] must be 0");
@@ -680,6 +681,7 @@ int lm_pq_attach_chunked(lm_index* ix, int32_t m, const int32_t* chunk_offsets, 
 
 int lm_pq_attach(lm_index* ix, int32_t m, const float* codebooks, const uint8_t* codes, int64_t ntotal) {
     if (!ix) LM_FAIL(LM_EINVAL, "NULL argument");
+    LM_NOT_ON_VIEW(ix, "lm_pq_attach");
     if (m <= 0 || m % 4 || ix->D % m) LM_FAIL(LM_EINVAL, "m must be a multiple of 4 that divides d");
     std::vector<int32_t> off((size_t)m + 1);
     for (int j = 0; j <= m; ++j) off[j] = j * (ix->D / m);  // uniform chunks: the same code path, the same arithmetic
@@ -747,6 +749,7 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
 // Everything lm_pq_batch_search_filtered* rejects, in front of any staging or launch: pq_search_device's argument and state checks (it repeats them), then
 // what pq_search_pass and the rerank tail would refuse after their first launches -- the beam width, the LDS rule of the filtered kernel, the rerank sort.
 static int pq_filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm_pq_search_params* params) {
+    LM_NOT_ON_VIEW(ix, "lm_pq_batch_search_filtered");
     if (!ix || !params || n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad search arguments");
     if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
     if (params->recompute_neighbors)
@@ -805,6 +808,7 @@ int lm_pq_batch_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t
 
 int lm_pq_batch_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const lm_pq_search_params* params,
                               int64_t* d_labels, float* d_distances) {
+    LM_NOT_ON_VIEW(ix, "lm_pq_batch_search_device");
     if (n > 0 && (!d_x || !d_labels || !d_distances)) LM_FAIL(LM_EINVAL, "NULL buffer");
     return pq_search_device(ix, n, d_x, k, params, d_labels, d_distances);
 }
@@ -812,6 +816,7 @@ int lm_pq_batch_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t
 int lm_pq_batch_search(lm_index* ix, int64_t n, const float* x, int32_t k, const lm_pq_search_params* params, int64_t* labels,
                        float* distances) {
     if (!ix) LM_FAIL(LM_EINVAL, "NULL index");
+    LM_NOT_ON_VIEW(ix, "lm_pq_batch_search");
     if (n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad n / k");
     if (n == 0) return LM_OK;
     if (!x || !labels || !distances) LM_FAIL(LM_EINVAL, "NULL buffer");

@@ -15,6 +15,7 @@
 //   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
 //   lm_filter_impl.h  allow-list for the graph search (lm_index_search_filtered*): k_filter_collect, once per lock-step round before k_update
 //   lm_link_impl.h    index build time: link insertion (lm_graph_add_links): k_link_count / k_link_scan / k_link_fill / k_link_row
+//   lm_view_impl.h    lm_index_create_view: k_search_table's dense-level graph accessor (fixed-capacity level adjacencies searched in place)
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
@@ -40,6 +41,7 @@ void set_error(const std::string& msg) { g_err = msg; }
 #include "lm_kernels_expand.h"
 #include "lm_kernels_prune.h"
 #include "lm_kernels_update.h"
+#include "lm_view_impl.h"
 #include "lm_kernels_persist.h"
 #include "lm_kernels_misc.h"
 #include "lm_filter_impl.h"
@@ -60,6 +62,10 @@ struct lm_index {
     uint64_t* d_level_ptr = nullptr;
     int32_t* d_neighbors = nullptr;
     L0Range* d_l0 = nullptr;
+    // lm_index_create_view: the graph is the caller's level adjacencies, read in place (none of the four CSR arrays above exists)
+    bool view = false;
+    std::vector<lm_graph_level> view_levels;  // the descriptors as given (device pointers, borrowed)
+    ViewLevelDev* d_view_up = nullptr;        // levels 1 .. max_level for the kernel; the one device allocation a view owns for its graph
     // PQ (DiskANN-style path)
     int32_t pq_m = 0;
     float* d_pq_codebooks = nullptr;
@@ -135,6 +141,12 @@ struct lm_index {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_update, ev_expand, ev_provider;
     std::vector<hipEvent_t> ev_pool;
 };
+
+// entry points that read the CSR arrays (or state only a CSR index can have) refuse a view before they stage or launch anything
+#define LM_NOT_ON_VIEW(ix, what) \
+    do { \
+        if ((ix) && (ix)->view) LM_FAIL(LM_ESTATE, std::string(what) + " is not served by a view index (lm_index_create_view): build a CSR index for it"); \
+    } while (0)
 
 static int free_ws(lm_index* ix) {
     for (void* p : ix->ws_allocs) (void)hipFree(p);
@@ -338,23 +350,24 @@ static int launch_filter_collect(lm_index* ix, const UpdateArgs& a, bool f16, co
 // 1 / 0 forces either, -1 (default) = wave when the expected new-list per hop (beam x mean level-0 degree) fits one pass of a
 // wave's row groups comfortably (<= 24) and there are enough queries to fill the chip with waves (B >= 2048)
 static bool persist_wave_form(const lm_index* ix) {
+    if (ix->view) return ix->persistent_wave == 1;  // a view knows no mean degree: auto = the workgroup form
     if (ix->persistent_wave >= 0) return ix->persistent_wave != 0;
     return ix->ws.B >= 2048 && ix->ws.W * ix->avg_degree0 <= 24.0;
 }
 
-template <bool L2, bool F16>
-static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GraphDev& g, size_t shmem) {
+template <bool L2, bool F16, class GA>
+static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GA& g, size_t shmem) {
     dim3 grid(ix->ws.B);
     const bool wave = persist_wave_form(ix);
     switch (ix->Dp / 64) {
 #define CASEP(n)                                                                                                         \
     case n:                                                                                                              \
         if (wave) {                                                                                                      \
-            LM_HIP(hipFuncSetAttribute((const void*)k_search_table<n, L2, F16, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-            hipLaunchKernelGGL((k_search_table<n, L2, F16, 64>), grid, dim3(64), shmem, ix->stream, g, ix->ws, a);        \
+            LM_HIP(hipFuncSetAttribute((const void*)k_search_table<n, L2, F16, 64, GA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+            hipLaunchKernelGGL((k_search_table<n, L2, F16, 64, GA>), grid, dim3(64), shmem, ix->stream, g, ix->ws, a);        \
         } else {                                                                                                         \
-            LM_HIP(hipFuncSetAttribute((const void*)k_search_table<n, L2, F16, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-            hipLaunchKernelGGL((k_search_table<n, L2, F16, 256>), grid, dim3(256), shmem, ix->stream, g, ix->ws, a);      \
+            LM_HIP(hipFuncSetAttribute((const void*)k_search_table<n, L2, F16, 256, GA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+            hipLaunchKernelGGL((k_search_table<n, L2, F16, 256, GA>), grid, dim3(256), shmem, ix->stream, g, ix->ws, a);      \
         }                                                                                                                \
         break
         CASEP(1); CASEP(2); CASEP(3); CASEP(4); CASEP(5); CASEP(6); CASEP(8); CASEP(12); CASEP(16);
@@ -362,6 +375,27 @@ static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GraphDev
         default: LM_FAIL(LM_EINVAL, "unsupported padded dimension (supported: 64..384, 512, 768, 1024)");
     }
     LM_HIP(hipGetLastError());
+    return LM_OK;
+}
+
+#define VIEW_LDS_TEXT "efSearch / k / beam_size too large for a view index: (2*max(efSearch,k) + P(maxnew)) * 8 + 4 * maxnew bytes, maxnew = max(beam_size * levels[0].cap, largest upper cap, 1), must fit 150 KiB"
+
+// Everything a search on a view refuses, in front of any staging or launch (NULL / range errors of the arguments are left to do_search_device,
+// which reports them for every index alike).
+static int view_checks(const lm_index* ix, int64_t n, int32_t k, const lm_search_params* prm) {
+    if (!ix || !ix->view || !prm || n <= 0 || k <= 0 || prm->efSearch <= 0 || prm->batch_size < 0) return LM_OK;
+    if (prm->recompute) LM_FAIL(LM_ESTATE, "a view index searches stored embeddings only: recompute = 1 is not served (lm_index_create_view)");
+    if (prm->batch_size > 0) LM_FAIL(LM_ESTATE, "a view index has no dynamic batching: batch_size > 0 is not served (lm_index_create_view)");
+    if (prm->pq_pruning_ratio > 0.0f) LM_FAIL(LM_ESTATE, "a view index has no two-level search: pq_pruning_ratio > 0 is not served (lm_index_create_view)");
+    if (!ix->persistent_table) LM_FAIL(LM_ESTATE, "a view index has no lock-step search: option persistent_table = 0 is not served (lm_index_create_view)");
+    if (ix->N == 0) return LM_OK;  // the empty values, whatever is attached
+    if (!ix->d_table) LM_FAIL(LM_ESTATE, "a view index needs a stored-embedding table (lm_index_attach_table)");
+    const int64_t W = std::max(prm->beam_size, 1);
+    if (W > 64) LM_FAIL(LM_EINVAL, "beam_size > 64 is not supported by the persistent search kernel, the only one a view index has");
+    const int64_t maxnew = std::max<int64_t>({W * ix->maxdeg0, (int64_t)ix->maxdeg_up, (int64_t)1});
+    int64_t P = 1;
+    while (P < maxnew) P <<= 1;
+    if ((2 * (int64_t)std::max(prm->efSearch, k) + P) * 8 + 4 * maxnew > 150 * 1024) LM_FAIL(LM_EINVAL, VIEW_LDS_TEXT);
     return LM_OK;
 }
 
@@ -387,20 +421,26 @@ static int search_pass_persistent(lm_index* ix, int32_t B, const float* d_q, int
         LM_HIP(hipMalloc((void**)&ix->d_pq_rounds, (size_t)B * 4));
         ix->pq_cap = B;
     }
-    GraphDev g{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets, ix->d_level_ptr, ix->d_neighbors, ix->d_l0};
     PersistArgs a{};
     a.Q = d_q; a.E = ix->d_table; a.check_rel = prm.check_relative_distance; a.max_level = ix->max_level;
     a.Pmax = next_pow2(ws.maxnew); a.k = k; a.metric = ix->metric; a.labels = d_labels; a.dist = d_dist;
     a.rounds_q = ix->d_pq_rounds;
     const size_t shmem = ((size_t)2 * ef + a.Pmax) * 8 + (size_t)ws.maxnew * 4;
-    if (shmem > 150 * 1024) return 1;  // caller falls back to the lock-step path
+    if (shmem > 150 * 1024) {
+        if (ix->view) LM_FAIL(LM_EINVAL, VIEW_LDS_TEXT);  // (view_checks refuses this before anything is staged; there is no lock-step form of a view)
+        return 1;  // caller falls back to the lock-step path
+    }
     LM_HIP(hipMemsetAsync(ws.visited, 0, (size_t)B * ws.nw * 4, st));
     LM_HIP(hipMemsetAsync(ws.counters, 0, C_NCOUNTERS * sizeof(unsigned long long), st));
     {
         EvScope es(ix, &ix->ev_update);
         const bool f16 = ix->table_dtype == LM_DTYPE_F16, l2 = ix->metric == LM_METRIC_L2;
-        rc = l2 ? (f16 ? launch_persist_nch<true, true>(ix, a, g, shmem) : launch_persist_nch<true, false>(ix, a, g, shmem))
-                : (f16 ? launch_persist_nch<false, true>(ix, a, g, shmem) : launch_persist_nch<false, false>(ix, a, g, shmem));
+        auto go = [&](const auto& g) {
+            return l2 ? (f16 ? launch_persist_nch<true, true>(ix, a, g, shmem) : launch_persist_nch<true, false>(ix, a, g, shmem))
+                      : (f16 ? launch_persist_nch<false, true>(ix, a, g, shmem) : launch_persist_nch<false, false>(ix, a, g, shmem));
+        };
+        if (ix->view) rc = go(ViewDev{ix->N, ix->entry_point, ix->max_level, ix->view_levels[0].d_adj, ix->view_levels[0].cap, ix->d_view_up});
+        else rc = go(GraphDev{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets, ix->d_level_ptr, ix->d_neighbors, ix->d_l0});
     }
     if (rc) return rc;
     ix->stats.update_launches++;
@@ -647,6 +687,7 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     lm_search_params prm = *params;
     if (prm.efSearch <= 0) LM_FAIL(LM_EINVAL, "efSearch must be positive");
     if (prm.batch_size < 0) LM_FAIL(LM_EINVAL, "batch_size must not be negative (0 = no dynamic batching)");
+    if (int vrc = view_checks(ix, n, k, &prm)) return vrc;
     LM_HIP(hipSetDevice(ix->device));
     if (flt) ix->filtered_allowed_evals = 0;
     ix->stats = lm_search_stats{};
@@ -687,8 +728,8 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     int64_t nwbytes = ((ix->N + 31) / 32) * 4;
     maxb = std::max<int64_t>(1, std::min<int64_t>(maxb, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));
     // the persistent launch's condition (search_pass_persistent declines when its LDS does not fit: its own check, restated for the filtered search)
-    const bool persistent = !prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table && ix->update_variant == 0 &&
-                            std::max(prm.beam_size, 1) <= 64;
+    const bool persistent = ix->view || (!prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table &&
+                                         ix->update_variant == 0 && std::max(prm.beam_size, 1) <= 64);  // (a view: view_checks has established the rest)
     FilterPass fpass{};
     if (flt) {
         // The stats of a filtered call are those of lm_index_search on the same inputs.  Where that call runs the persistent launch, its nrounds
@@ -705,6 +746,7 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
         // (a filtered search collects its result round by round: lock-step too)
         if (!flt && persistent)
             rc = search_pass_persistent(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k);
+        if (rc == 1 && ix->view) LM_FAIL(LM_ESTATE, "internal: a view index has no lock-step search");
         if (rc == 1)  // not applicable (or LDS budget exceeded): lock-step rounds
             rc = search_pass(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k, flt);
         if (rc) return rc;
@@ -846,6 +888,66 @@ int lm_index_read(const char* path, int device, lm_index** out) {
     return rc;
 }
 
+int lm_index_create_view(int64_t ntotal, int32_t d, int32_t metric, const lm_graph_level* levels, int32_t n_levels, int32_t entry_point, int device,
+                         lm_index** out) {
+    if (!out) LM_FAIL(LM_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (!levels) LM_FAIL(LM_EINVAL, "levels is NULL");
+    if (n_levels < 1) LM_FAIL(LM_EINVAL, "n_levels must be at least 1");
+    if (ntotal < 0 || ntotal > 0x7fffffffll) LM_FAIL(LM_EINVAL, "ntotal must be in [0, INT32_MAX]");
+    if (metric != LM_METRIC_L2 && metric != LM_METRIC_INNER_PRODUCT) LM_FAIL(LM_EINVAL, "unknown metric");
+    if (d <= 0 || d > 1024) LM_FAIL(LM_EINVAL, "unsupported dimension (padded to a multiple of 64: 64..384, 512, 768, 1024)");
+    switch ((d + 63) / 64) {
+        case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 12: case 16: break;
+        default: LM_FAIL(LM_EINVAL, "unsupported dimension (padded to a multiple of 64: 64..384, 512, 768, 1024)");
+    }
+    int64_t nn = 0;
+    int32_t cap_up = 0;
+    for (int32_t l = 0; l < n_levels; ++l) {
+        const lm_graph_level& L = levels[l];
+        const std::string at = "levels[" + std::to_string(l) + "]: ";
+        if (L.cap < 1) LM_FAIL(LM_EINVAL, at + "cap must be at least 1");
+        if (L.n_rows < 0 || L.n_rows > ntotal) LM_FAIL(LM_EINVAL, at + "n_rows must be in [0, ntotal]");
+        if (l == 0 && (L.d_nodes || L.n_rows != ntotal)) LM_FAIL(LM_EINVAL, "levels[0] must be the identity level: d_nodes NULL and n_rows == ntotal");
+        if (l > 0 && L.n_rows > 0 && !L.d_nodes && L.n_rows != ntotal) LM_FAIL(LM_EINVAL, at + "d_nodes is NULL but n_rows != ntotal");
+        if (L.n_rows > 0 && !L.d_adj) LM_FAIL(LM_EINVAL, at + "d_adj is NULL");
+        nn += L.n_rows * (int64_t)L.cap;
+        if (l > 0) cap_up = std::max(cap_up, L.cap);
+    }
+    if (ntotal > 0 && (entry_point < 0 || entry_point >= ntotal)) LM_FAIL(LM_EINVAL, "entry_point out of range");
+    int ndev = lm_device_count();
+    if (ndev <= 0) LM_FAIL(LM_EHIP, "no HIP device visible: libleann_mi355x requires an MI355X (gfx950) GPU");
+    if (device < 0 || device >= ndev) LM_FAIL(LM_EINVAL, "device index out of range");
+    LM_HIP(hipSetDevice(device));
+    lm_index* ix = new lm_index();
+    ix->device = device;
+    ix->view = true;
+    ix->view_levels.assign(levels, levels + n_levels);
+    ix->N = ntotal; ix->D = d; ix->Dp = (d + 63) / 64 * 64; ix->metric = metric;
+    ix->entry_point = ntotal > 0 ? entry_point : -1;
+    ix->max_level = n_levels - 1;
+    ix->maxdeg0 = levels[0].cap;
+    ix->maxdeg_up = cap_up;
+    ix->n_neighbors = nn;
+    std::vector<ViewLevelDev> up;
+    for (int32_t l = 1; l < n_levels; ++l) up.push_back(ViewLevelDev{levels[l].d_nodes, levels[l].d_adj, (int32_t)levels[l].n_rows, levels[l].cap});
+    hipError_t e = hipSuccess;
+    if (!up.empty() && ((e = hipMalloc((void**)&ix->d_view_up, up.size() * sizeof(ViewLevelDev))) != hipSuccess ||
+                        (e = hipMemcpy(ix->d_view_up, up.data(), up.size() * sizeof(ViewLevelDev), hipMemcpyHostToDevice)) != hipSuccess)) {
+        set_error(std::string("level descriptor upload failed: ") + hipGetErrorString(e));
+        lm_index_free(ix);
+        return LM_EHIP;
+    }
+    if (hipHostMalloc((void**)&ix->h_counters, C_NCOUNTERS * sizeof(unsigned long long)) != hipSuccess) {
+        set_error("hipHostMalloc failed");
+        lm_index_free(ix);
+        return LM_EHIP;
+    }
+    std::memset(ix->h_counters, 0, C_NCOUNTERS * sizeof(unsigned long long));
+    *out = ix;
+    return LM_OK;
+}
+
 void lm_index_free(lm_index* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
@@ -854,6 +956,7 @@ void lm_index_free(lm_index* ix) {
     if (ix->d_level_ptr) (void)hipFree(ix->d_level_ptr);
     if (ix->d_neighbors) (void)hipFree(ix->d_neighbors);
     if (ix->d_l0) (void)hipFree(ix->d_l0);
+    if (ix->d_view_up) (void)hipFree(ix->d_view_up);  // a view's level arrays themselves are the caller's
     if (ix->d_memo_slot) (void)hipFree(ix->d_memo_slot);
     if (ix->d_memo) (void)hipFree(ix->d_memo);
     if (ix->d_hub_slot_init) (void)hipFree(ix->d_hub_slot_init);
@@ -933,6 +1036,7 @@ int lm_index_attach_table(lm_index* ix, const void* table, int32_t dtype, int64_
 
 int lm_index_set_hub_cache(lm_index* ix, const int32_t* ids, int32_t n, const float* d_embeddings) {
     if (!ix) LM_FAIL(LM_EINVAL, "NULL index");
+    LM_NOT_ON_VIEW(ix, "lm_index_set_hub_cache");
     LM_HIP(hipSetDevice(ix->device));
     if (n == 0) {
         ix->hub_n = 0;
@@ -1094,7 +1198,7 @@ int lm_index_get_stats(const lm_index* ix, lm_search_stats* out) {
 int lm_index_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, float* d_distances, int64_t* d_labels,
                            const lm_search_params* params) {
     if (n > 0 && (!d_x || !d_distances || !d_labels)) LM_FAIL(LM_EINVAL, "NULL buffer");
-    return do_search_device(ix, n, d_x, k, d_distances, d_labels, params);
+    return do_search_device(ix, n, d_x, k, d_distances, d_labels, params);  // (a view's refusals: view_checks, in front of its first launch)
 }
 
 int lm_index_search(lm_index* ix, int64_t n, const float* x, int32_t k, float* distances, int64_t* labels,
@@ -1103,6 +1207,7 @@ int lm_index_search(lm_index* ix, int64_t n, const float* x, int32_t k, float* d
     if (n < 0 || k <= 0) LM_FAIL(LM_EINVAL, "bad n / k");
     if (n == 0) return LM_OK;
     if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
+    if (int vrc = view_checks(ix, n, k, params)) return vrc;
     LM_HIP(hipSetDevice(ix->device));
     const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
     if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
@@ -1143,6 +1248,7 @@ static int filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm_se
 
 int lm_index_search_filtered_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const uint32_t* d_allow, float* d_distances,
                                     int64_t* d_labels, const lm_search_params* params) {
+    LM_NOT_ON_VIEW(ix, "lm_index_search_filtered_device");
     if (int rc = filtered_checks(ix, n, k, params)) return rc;
     if (n > 0 && (!d_x || !d_distances || !d_labels)) LM_FAIL(LM_EINVAL, "NULL buffer");
     const FilterPass flt{d_allow};
@@ -1151,6 +1257,7 @@ int lm_index_search_filtered_device(lm_index* ix, int64_t n, const float* d_x, i
 
 int lm_index_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t k, const uint32_t* allow, float* distances, int64_t* labels,
                              const lm_search_params* params) {
+    LM_NOT_ON_VIEW(ix, "lm_index_search_filtered");
     if (int rc = filtered_checks(ix, n, k, params)) return rc;
     FilterPass flt{nullptr};
     if (n == 0) return do_search_device(ix, 0, nullptr, k, nullptr, nullptr, params, &flt);  // the stats of an empty call

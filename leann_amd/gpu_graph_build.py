@@ -395,6 +395,68 @@ def _assemble_csr(levels_top: np.ndarray, graphs: "list[tuple[np.ndarray, np.nda
                    ef_construction=efc, cum_nneighbor_per_level=cum)
 
 
+SEARCHES = ("csr", "view")
+
+
+class _LevelView:
+    """The candidate search of build_graph_gpu(search="view"): ONE lm_index per level being built, a live view (lm_index_create_view) of
+    the level's own adjacency -- ``G.adj``, which lm_graph_add_links, clear_rows and seed_rows update in place -- and of the finished
+    levels above it, with the table attached once.  Every insert batch then searches what is there: no host copy of the adjacencies, no
+    CSR assembly, no upload, no handle and workspace per batch.  Same parameters as hip_search_fn, hence (lm_index_create_view's
+    equivalence) the same candidate ids and similarities, bit for bit, as the search of the CSR that temp_csr() would have assembled."""
+
+    def __init__(self, G: "_LevelGraph", finished: "list[_LevelGraph]", xs: torch.Tensor, table: torch.Tensor, metric: int, entry_global: int,
+                 beam: int = 2):
+        from .index import Mi355xIndex
+
+        sub = G.sub
+        dev = sub.device
+        levels = [(None, G.adj)]
+        for f in finished:  # the upper levels, rows and ids mapped once into this level's local id space (they are small)
+            loc = torch.searchsorted(sub, f.sub)
+            m = f.adj >= 0
+            a = torch.full_like(f.adj, -1)
+            a[m] = loc[f.adj[m].to(torch.int64)].to(torch.int32)
+            levels.append((loc.to(torch.int32).contiguous(), a.contiguous()))
+        entry = int(torch.searchsorted(sub, torch.tensor([entry_global], dtype=sub.dtype, device=dev))[0])
+        self.metric = metric
+        self.idx = Mi355xIndex.from_levels(levels, sub.shape[0], xs.shape[1], metric, entry, device=dev.index or 0)
+        if table.is_cuda:
+            self.idx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        self._table = table  # borrowed by the handle
+        _lib_check_attach(self.idx, table, xs.shape[1])
+        self.beam = beam
+
+    def search(self, queries: torch.Tensor, ef: int, k: int):
+        """(ids [b, k] int64, sim [b, k]) -- hip_search_fn's contract, on the view."""
+        import ctypes as C
+
+        from . import _lib
+
+        q = queries.float().contiguous()
+        n = q.shape[0]
+        dist = torch.empty((n, k), dtype=torch.float32, device=q.device)
+        ids = torch.empty((n, k), dtype=torch.int64, device=q.device)
+        prm = self.idx.make_params(ef=ef, beam=self.beam, recompute=False, max_batch=16384)
+        # (Mi355xIndex.search_device without its is_cuda assertion: the host build of the library, which the CPU tests load, takes host pointers)
+        _lib.check(self.idx._lib.lm_index_search_device(self.idx._h, n, C.c_void_p(q.data_ptr()), k, C.c_void_p(dist.data_ptr()), C.c_void_p(ids.data_ptr()),
+                                                       C.byref(prm)), "lm_index_search_device")
+        return ids, (dist if self.metric == METRIC_INNER_PRODUCT else -dist)
+
+    def close(self):
+        self.idx.close()
+
+
+def _lib_check_attach(idx, table: torch.Tensor, d: int):
+    """Attach a padded fp32 / fp16 table that lives where the library's kernels run (borrowed: location 1)."""
+    import ctypes as C
+
+    from . import _lib
+
+    _lib.check(idx._lib.lm_index_attach_table(idx._h, C.c_void_p(table.data_ptr()), _lib.DTYPE_F16 if table.dtype == torch.float16 else _lib.DTYPE_F32,
+                                              table.shape[0], int(d), 1), "lm_index_attach_table")
+
+
 def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
     """Default candidate search: the HIP stored-embedding search (lm_index_search_device)."""
 
@@ -425,7 +487,7 @@ def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
 def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_construction: int = 200, seed: int = 12345,
                     search_fn: Optional[SearchFn] = None, growth: float = 1.5, k_cand: int = 0,
                     seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch",
-                    linker: str = "torch") -> HnswCsr:
+                    linker: str = "torch", search: str = "csr") -> HnswCsr:
     """x: [N, D] float tensor on the build device.  Returns the compact-CSR HNSW graph (host).  ``alpha`` > 1 relaxes the neighbour
     selection the way Vamana does (denser lists with longer edges: what a PQ-guided walk over a flat graph needs at 10M nodes -- DESIGN 8;
     inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on.
@@ -433,9 +495,19 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
     distances: a slightly different, oracle-pinned graph -- DESIGN.md).
     ``linker``: "torch" (default) = link insertion (_LevelGraph.add_links) by torch ops, "kernel" = by lm_graph_add_links.  The kernel
     shrinks overflowing lists with the canonical fp32 rule whatever ``selector`` is; with selector="kernel" both linkers build the same
-    graph byte for byte."""
+    graph byte for byte.
+    ``search``: "csr" (default) = every insert batch assembles the graph built so far as a CSR on the host, uploads it as a fresh index
+    and searches that (``search_fn``; by default hip_search_fn); "view" = one view index per level (lm_index_create_view) searches the
+    level adjacencies where lm_graph_add_links keeps them -- it needs linker="kernel" (the int32 adjacency updated in place) and takes no
+    ``search_fn``.  With selector="kernel" and linker="kernel" both build the same graph byte for byte."""
     select = _selector_fn(selector)
     _check_linker(linker)
+    if search not in SEARCHES:
+        raise ValueError(f"search must be one of {SEARCHES}, not {search!r}")
+    if search == "view" and linker != "kernel":
+        raise ValueError('search="view" needs linker="kernel": the view reads the int32 adjacency that lm_graph_add_links updates in place')
+    if search == "view" and search_fn is not None:
+        raise ValueError('search="view" searches through its own view index: it takes no search_fn')
     metric = metric.lower()
     if metric not in ("mips", "cosine", "l2"):
         raise ValueError(f"Unsupported distance_metric '{metric}'.")
@@ -445,7 +517,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
     if n == 0:
         return HnswCsr(d=d, ntotal=0, metric_type=mt, levels=np.zeros(0, np.int32), level_ptr=np.zeros(0, np.uint64),
                        node_offsets=np.zeros(1, np.uint64), neighbors=np.zeros(0, np.int32), entry_point=-1, max_level=-1)
-    if search_fn is None:
+    if search_fn is None and search == "csr":
         search_fn = hip_search_fn(dev.index or 0)
     k_cand = k_cand or min(ef_construction, 128)
     gen = torch.Generator(device="cpu").manual_seed(seed)
@@ -502,10 +574,17 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             graphs = [(sub_np, G.export())] + [(f.sub.cpu().numpy(), f.export()) for f in finished]
             return _assemble_csr(rel_top, graphs, sub_np, d, mt, entry_global, M, ef_construction)
 
+        view: "list[_LevelView]" = []  # search="view": this level's view index, created at the first insert batch
+
         def insert(batch: torch.Tensor, replace: bool):
-            g = temp_csr()
             kk = min(k_cand + (1 if replace else 0), max(int(inserted.sum()) - 1, 1))
-            ids, sim = search_fn(g, xs, xs[batch], max(ef_construction, kk), kk)
+            if search == "view":
+                if not view:  # the table as hip_search_fn attaches it: fp32, padded
+                    view.append(_LevelView(G, finished, xs, xlink if xlink.dtype == torch.float32 else _padded_table(xs.float()), mt, entry_global))
+                ids, sim = view[0].search(xs[batch], max(ef_construction, kk), kk)
+            else:
+                g = temp_csr()
+                ids, sim = search_fn(g, xs, xs[batch], max(ef_construction, kk), kk)
             ids = ids.to(dev)
             sim = sim.to(dev).float()
             if replace:  # refinement: drop self, merge with current links
@@ -552,6 +631,8 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 insert(allb[b0 : b0 + step], replace=True)
             if verbose:
                 print(f"[build] level {l}: refined, mean degree {float(G.deg.float().mean()):.1f}")
+        if view:
+            view[0].close()
         finished.insert(0, G)
 
     # final assembly over all nodes (level 0 subset == everything)

@@ -69,6 +69,33 @@ class Mi355xIndex:
         return idx
 
     @classmethod
+    def from_levels(cls, levels, ntotal: int, d: int, metric: int, entry_point: int, device: int = 0) -> "Mi355xIndex":
+        """A live view of device-resident level adjacencies (lm_index_create_view): nothing is copied, a search reads the tensors as they
+        are when its kernel runs.  ``levels``: one ``(nodes, adj)`` pair per level, level 0 first; ``adj`` an int32 device tensor
+        [n_rows, cap] in lm_graph_add_links' layout (a value outside [0, ntotal) = empty slot), ``nodes`` an int32 device tensor of the
+        n_rows node ids, ascending, or None for the identity (level 0 must be that).  The handle keeps references to the tensors, so
+        they outlive it; writing INTO them (in place, on the index's stream) is the point, replacing them is not seen."""
+        import torch
+
+        lib = _lib.load()
+        arr = (_lib.GraphLevel * max(len(levels), 1))()
+        keep = []
+        for l, (nodes, adj) in enumerate(levels):
+            if not (isinstance(adj, torch.Tensor) and adj.dtype == torch.int32 and adj.dim() == 2 and adj.is_contiguous()):
+                raise ValueError(f"levels[{l}]: adj must be a contiguous int32 tensor [n_rows, cap]")
+            if nodes is not None and not (isinstance(nodes, torch.Tensor) and nodes.dtype == torch.int32 and nodes.dim() == 1 and nodes.is_contiguous()
+                                          and nodes.shape[0] == adj.shape[0] and nodes.device == adj.device):
+                raise ValueError(f"levels[{l}]: nodes must be None or a contiguous int32 tensor [n_rows] beside adj")
+            arr[l] = _lib.GraphLevel(None if nodes is None or nodes.shape[0] == 0 else nodes.data_ptr(), None if adj.shape[0] == 0 else adj.data_ptr(),
+                                     adj.shape[0], adj.shape[1])
+            keep.append((nodes, adj))
+        h = C.c_void_p()
+        check(lib.lm_index_create_view(int(ntotal), int(d), int(metric), arr, len(levels), int(entry_point), device, C.byref(h)), "lm_index_create_view")
+        idx = cls(h)
+        idx._levels_keepalive = keep
+        return idx
+
+    @classmethod
     def read(cls, path: str, device: int = 0) -> "Mi355xIndex":
         """faiss.read_index(path, IO_FLAG_MMAP, HNSWIndexConfig) equivalent (hnsw_backend.py:145-151)."""
         lib = _lib.load()
