@@ -288,8 +288,13 @@ __device__ __forceinline__ void t4_outproj_slab(const unsigned char* b20, const 
 // 32 j + 8 q + 4 g + i, i.e. half of every fragment register pair trades places with the partner lane (token, g ^ 1).
 __device__ __forceinline__ void t4_ln1(float16v (&o)[ML_NJ], const half8 (&rf)[ML_KS], half8 (&xf)[ML_KS], const float* gam_s,
                                        const float* bet_s, int g, float eps) {
-    // ONE pass for both moments (sum and sum of squares of v = o + residual; var = E[v^2] - mean^2 in fp32 over 384 values of order 1),
-    // then y = (v rstd - mean rstd) gamma + beta as two packed fused multiply-adds per pair; gamma / beta are fp32 in LDS (no conversions).
+    // ONE pass for both moments (sum and sum of squares of v = o + residual; var = E[v^2] - mean^2 in fp32 over 384 values).  The subtraction loses about
+    // (mean / std)^2 x 2^-24 of the normalised value.  Measured on an MI355X against fp64 (tests/test_gpu_encoder_trained_like.py: max |diff| / scale of
+    // the layer's output; fp16 level = 3.9e-4), rows of this LayerNorm / of the epilogue's at mean / std 0: 3.9e-4 / 3.9e-4, 8: 6.0e-4 / 3.8e-4,
+    // 32: 5.8e-4 / 3.5e-4, 64: 6.9e-4 / 9.3e-4, 120: 7.1e-4 / 1.6e-3 (that module's cases); 250: 1.6e-3 / 8.6e-3, 400: 3.5e-3 / 2.2e-2, 1000: 2.4e-2 /
+    // 1.7e-1 (its _variance_case called by hand).  This LayerNorm leaves fp16 level at mean / std 8 (1.5 x; 1.8 x at 64 .. 120), the epilogue's between 32
+    // and 64 (2.4 x at 64, 4 x at 120); beyond 120 both grow with the square.
+    // Then y = (v rstd - mean rstd) gamma + beta as two packed fused multiply-adds per pair; gamma / beta are fp32 in LDS (no conversions).
     // 4.75 instructions per value against the 8.25 of the two-pass form with fp16 parameters: this phase runs with the matrix pipe idle.
     __builtin_amdgcn_sched_barrier(0);
     float2v sa = {0.f, 0.f}, sb = {0.f, 0.f}, qa = {0.f, 0.f}, qb = {0.f, 0.f};
