@@ -271,29 +271,11 @@ int lm_exact_search(const void* d_table, int32_t dtype, int64_t ntable, int32_t 
 // queries [n][D] on the device -> the kernel's [n][Dp] (the index's own padding buffer, as lm_index_search_device), workspace grown on demand
 static int exact_on_index(lm_index* ix, int64_t n, const float* d_x, int32_t k, const uint32_t* d_allow, float* d_dist, int64_t* d_labels) {
     hipStream_t st = ix->stream;
-    const float* d_q = d_x;
-    if (ix->D != ix->Dp) {
-        if (n > ix->qpad_cap) {
-            if (ix->d_qpad) (void)hipFree(ix->d_qpad);
-            ix->d_qpad = nullptr;
-            ix->qpad_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_qpad, (size_t)n * ix->Dp * sizeof(float)));
-            ix->qpad_cap = n;
-        }
-        const int64_t tot = n * ix->Dp;
-        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_x, n, ix->D, ix->Dp, ix->d_qpad);
-        d_q = ix->d_qpad;
-    }
-    const size_t need = lm_exact_search_workspace_bytes(ix->N, n, k);
-    if (need > ix->exact_ws_bytes) {
-        if (ix->d_exact_ws) (void)hipFree(ix->d_exact_ws);
-        ix->d_exact_ws = nullptr;
-        ix->exact_ws_bytes = 0;
-        LM_HIP(hipMalloc(&ix->d_exact_ws, need));
-        ix->exact_ws_bytes = need;
-    }
-    if (int rc = lm_exact_search(ix->d_table, ix->table_dtype, ix->N, ix->Dp, ix->metric, d_q, n, k, d_allow, d_dist, d_labels, ix->d_exact_ws,
-                                 ix->exact_ws_bytes, st))
+    const float* d_q = nullptr;
+    if (int rc = pad_queries(ix, n, d_x, &d_q)) return rc;
+    if (int rc = ix->d_exact_ws.reserve(lm_exact_search_workspace_bytes(ix->N, n, k))) return rc;
+    if (int rc = lm_exact_search(ix->d_table, ix->table_dtype, ix->N, ix->Dp, ix->metric, d_q, n, k, d_allow, d_dist, d_labels, ix->d_exact_ws.get(),
+                                 ix->d_exact_ws.capacity(), st))
         return rc;
     LM_HIP(hipStreamSynchronize(st));
     return LM_OK;
@@ -321,27 +303,11 @@ int lm_index_search_exact(lm_index* ix, int64_t n, const float* x, int32_t k, co
     if (n == 0) return LM_OK;
     if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
     LM_HIP(hipSetDevice(ix->device));
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
-    uint32_t* d_allow = nullptr;
-    if (allow) {
-        if (allow_bytes > ix->exact_allow_bytes) {
-            if (ix->d_exact_allow) (void)hipFree(ix->d_exact_allow);
-            ix->d_exact_allow = nullptr;
-            ix->exact_allow_bytes = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_exact_allow, std::max<size_t>(allow_bytes, 16)));
-            ix->exact_allow_bytes = std::max<size_t>(allow_bytes, 16);
-        }
-        d_allow = ix->d_exact_allow;
-        if (allow_bytes) LM_HIP(hipMemcpyAsync(d_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
-    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
-    if (int rc = exact_on_index(ix, n, ix->d_stage_x, k, d_allow, ix->d_stage_d, ix->d_stage_l)) return rc;
-    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipStreamSynchronize(ix->stream));
-    return LM_OK;
+    const uint32_t* d_allow = nullptr;
+    if (int rc = upload_allow(ix, allow, &d_allow)) return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = exact_on_index(ix, n, ix->d_stage_x.get(), k, d_allow, ix->d_stage_d.get(), ix->d_stage_l.get())) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 }  // extern "C"

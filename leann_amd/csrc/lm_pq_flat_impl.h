@@ -441,19 +441,8 @@ static int pq_flat_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, 
         LM_HIP(hipStreamSynchronize(st));
         return LM_OK;
     }
-    const float* d_q = d_x;
-    if (ix->D != ix->Dp) {
-        if (n > ix->qpad_cap) {
-            if (ix->d_qpad) (void)hipFree(ix->d_qpad);
-            ix->d_qpad = nullptr;
-            ix->qpad_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_qpad, (size_t)n * ix->Dp * sizeof(float)));
-            ix->qpad_cap = n;
-        }
-        const int64_t tot = n * ix->Dp;
-        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_x, n, ix->D, ix->Dp, ix->d_qpad);
-        d_q = ix->d_qpad;
-    }
+    const float* d_q = nullptr;
+    if (int rc = pad_queries(ix, n, d_x, &d_q)) return rc;
     const bool rerank = !prm.skip_search_reorder && ((prm.use_deferred_fetch && ix->provider) || ix->d_table != nullptr);
     const int64_t nwbytes = ((ix->N + 31) / 32) * 4;
     const int64_t maxb = std::max<int64_t>(1, std::min<int64_t>(4096, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));  // passes as pq_search_device cuts them
@@ -463,18 +452,12 @@ static int pq_flat_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, 
         PqFlatPlan p;
         if (int rc = pq_flat_validate(ix->N, ix->pq_m, ix->h_pq_chunk_off.data(), ix->D, ix->metric, B, ix->Dp, L, off, p)) return rc;
         if (int rc = ensure_ws(ix, B, L, 1)) return rc;
-        const size_t need = lm_pq_scan_workspace_bytes(ix->N, B, ix->pq_m, L);
-        if (need > ix->pqflat_ws_bytes) {
-            if (ix->d_pqflat_ws) (void)hipFree(ix->d_pqflat_ws);
-            ix->d_pqflat_ws = nullptr;
-            ix->pqflat_ws_bytes = 0;
-            LM_HIP(hipMalloc(&ix->d_pqflat_ws, need));
-            ix->pqflat_ws_bytes = need;
-        }
+        if (int rc = ix->d_pqflat_ws.reserve(lm_pq_scan_workspace_bytes(ix->N, B, ix->pq_m, L))) return rc;
         WsDev& ws = ix->ws;
         LM_HIP(hipMemsetAsync(ws.counters, 0, C_NCOUNTERS * sizeof(unsigned long long), st));
         PqFlatArgs a{};
-        a.codes = ix->d_pq_codes; a.codebooks = ix->d_pq_codebooks; a.Q = d_q + (size_t)o * ix->Dp; a.allow = d_allow; a.part = (uint64_t*)ix->d_pqflat_ws;
+        a.codes = ix->d_pq_codes.get(); a.codebooks = ix->d_pq_codebooks.get(); a.Q = d_q + (size_t)o * ix->Dp; a.allow = d_allow;
+        a.part = (uint64_t*)ix->d_pqflat_ws.get();
         a.ntotal = ix->N; a.nq = B; a.m = ix->pq_m; a.metric = ix->metric; a.ldq = ix->Dp; a.L = L;
         {
             EvScope es(ix, &ix->ev_update);
@@ -499,7 +482,7 @@ static int pq_flat_index_checks(lm_index* ix, int64_t n, int32_t k, const lm_pq_
     if (params->recompute_neighbors) LM_FAIL(LM_EINVAL, "recompute_neighbors != 0 is not supported (as in lm_pq_batch_search)");
     if (std::max(params->complexity, k) > LM_PQ_FLAT_MAX_L)
         LM_FAIL(LM_EINVAL, "max(complexity, k) must be at most LM_PQ_FLAT_MAX_L = " + std::to_string(LM_PQ_FLAT_MAX_L));
-    if (!ix->d_pq_codes) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
+    if (!ix->d_pq_codes.get()) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
     if (params->use_deferred_fetch && !ix->provider && !ix->d_table)
         LM_FAIL(LM_ESTATE, "deferred fetch requested but neither an embedding provider nor stored embeddings are attached");
     PqFlatOff off;  // the scan's own envelope (table + lists in the LDS), here so that nothing is staged or launched before it is known to hold
@@ -525,28 +508,11 @@ int lm_pq_flat_search(lm_index* ix, int64_t n, const float* x, int32_t k, const 
         ix->stats = lm_search_stats{};
         return LM_OK;
     }
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
-    uint32_t* d_allow = nullptr;
-    if (allow) {
-        if (allow_bytes > ix->pqflat_allow_bytes) {
-            if (ix->d_pqflat_allow) (void)hipFree(ix->d_pqflat_allow);
-            ix->d_pqflat_allow = nullptr;
-            ix->pqflat_allow_bytes = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_pqflat_allow, std::max<size_t>(allow_bytes, 16)));
-            ix->pqflat_allow_bytes = std::max<size_t>(allow_bytes, 16);
-        }
-        d_allow = ix->d_pqflat_allow;
-        if (allow_bytes) LM_HIP(hipMemcpyAsync(d_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
-        else LM_HIP(hipMemsetAsync(d_allow, 0, 16, ix->stream));
-    }
-    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
-    if (int rc = pq_flat_device(ix, n, ix->d_stage_x, k, params, d_allow, ix->d_stage_l, ix->d_stage_d)) return rc;
-    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipStreamSynchronize(ix->stream));
-    return LM_OK;
+    const uint32_t* d_allow = nullptr;  // (an empty index: no word to upload, and pq_flat_device launches nothing that reads the list)
+    if (int rc = upload_allow(ix, allow, &d_allow)) return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = pq_flat_device(ix, n, ix->d_stage_x.get(), k, params, d_allow, ix->d_stage_l.get(), ix->d_stage_d.get())) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 }  // extern "C"

@@ -606,22 +606,13 @@ static int pq_search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, 
     if (rc) return rc;
     WsDev& ws = ix->ws;
     hipStream_t st = ix->stream;
-    if ((int64_t)B > ix->pq_cap) {
-        if (ix->d_pq_nadc) (void)hipFree(ix->d_pq_nadc);
-        if (ix->d_pq_rounds) (void)hipFree(ix->d_pq_rounds);
-        ix->d_pq_nadc = nullptr;
-        ix->d_pq_rounds = nullptr;
-        ix->pq_cap = 0;
-        LM_HIP(hipMalloc((void**)&ix->d_pq_nadc, (size_t)B * 8));
-        LM_HIP(hipMalloc((void**)&ix->d_pq_rounds, (size_t)B * 4));
-        ix->pq_cap = B;
-    }
-    GraphDev g{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets, ix->d_level_ptr, ix->d_neighbors, ix->d_l0};
-    PqDev pq{ix->pq_m, ix->d_pq_chunk_off, ix->d_pq_codebooks, ix->d_pq_codes};
+    if ((rc = ensure_pq_counters(ix, B)) != LM_OK) return rc;
+    GraphDev g{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets.get(), ix->d_level_ptr.get(), ix->d_neighbors.get(), ix->d_l0.get()};
+    PqDev pq{ix->pq_m, ix->d_pq_chunk_off.get(), ix->d_pq_codebooks.get(), ix->d_pq_codes.get()};
     PqArgs pa{};
     pa.Q = d_q; pa.Dp = ix->Dp; pa.metric = ix->metric; pa.L = L; pa.W = W; pa.maxnew = ws.maxnew;
     pa.Pmax = next_pow2(ws.maxnew);
-    pa.n_adc_q = ix->d_pq_nadc; pa.rounds_q = ix->d_pq_rounds;
+    pa.n_adc_q = ix->d_pq_nadc.get(); pa.rounds_q = ix->d_pq_rounds.get();
     pa.exp_cap = exp_cap;
     pa.n_exp_overflow = ws.counters + C_PQ_OVERFLOW;
     pa.allow = flt ? flt->d_allow : nullptr;
@@ -661,19 +652,16 @@ int lm_pq_attach_chunked(lm_index* ix, int32_t m, const int32_t* chunk_offsets, 
         if (chunk_offsets[j + 1] < chunk_offsets[j]) LM_FAIL(LM_EINVAL, "chunk_offsets must not decrease");
     if (chunk_offsets[m] > ix->D) LM_FAIL(LM_EINVAL, "chunk_offsets[m] exceeds the index dimension");
     LM_HIP(hipSetDevice(ix->device));
-    if (ix->d_pq_codebooks) (void)hipFree(ix->d_pq_codebooks);
-    if (ix->d_pq_codes) (void)hipFree(ix->d_pq_codes);
-    if (ix->d_pq_chunk_off) (void)hipFree(ix->d_pq_chunk_off);
-    ix->d_pq_codebooks = nullptr;
-    ix->d_pq_codes = nullptr;
-    ix->d_pq_chunk_off = nullptr;
+    ix->d_pq_codebooks.release();  // a second attach: all three freed before any is allocated again
+    ix->d_pq_codes.release();
+    ix->d_pq_chunk_off.release();
     const size_t cb_bytes = (size_t)256 * chunk_offsets[m] * 4, code_bytes = (size_t)ntotal * m;
-    LM_HIP(hipMalloc((void**)&ix->d_pq_codebooks, std::max<size_t>(cb_bytes, 16)));
-    LM_HIP(hipMalloc((void**)&ix->d_pq_codes, std::max<size_t>(code_bytes, 16)));
-    LM_HIP(hipMalloc((void**)&ix->d_pq_chunk_off, (size_t)(m + 1) * 4));
-    LM_HIP(hipMemcpy(ix->d_pq_codebooks, codebooks, cb_bytes, hipMemcpyHostToDevice));
-    LM_HIP(hipMemcpy(ix->d_pq_codes, codes, code_bytes, hipMemcpyHostToDevice));
-    LM_HIP(hipMemcpy(ix->d_pq_chunk_off, chunk_offsets, (size_t)(m + 1) * 4, hipMemcpyHostToDevice));
+    if (int rc = ix->d_pq_codebooks.reserve(cb_bytes / 4, 4)) return rc;
+    if (int rc = ix->d_pq_codes.reserve(code_bytes, 16)) return rc;
+    if (int rc = ix->d_pq_chunk_off.reserve((size_t)m + 1)) return rc;
+    LM_HIP(hipMemcpy(ix->d_pq_codebooks.get(), codebooks, cb_bytes, hipMemcpyHostToDevice));
+    LM_HIP(hipMemcpy(ix->d_pq_codes.get(), codes, code_bytes, hipMemcpyHostToDevice));
+    LM_HIP(hipMemcpy(ix->d_pq_chunk_off.get(), chunk_offsets, (size_t)(m + 1) * 4, hipMemcpyHostToDevice));
     ix->pq_m = m;
     ix->h_pq_chunk_off.assign(chunk_offsets, chunk_offsets + m + 1);  // the flat scan takes them as a kernel argument
     return LM_OK;
@@ -703,7 +691,7 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
     if (params->recompute_neighbors)
         LM_FAIL(LM_EINVAL, "recompute_neighbors != 0 is not supported: the traversal runs on PQ distances only, as the reference runs it (diskann_backend.py:444-451)");
-    if (!ix->d_pq_codes) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
+    if (!ix->d_pq_codes.get()) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
     if (params->use_deferred_fetch && !ix->provider && !ix->d_table)
         LM_FAIL(LM_ESTATE, "deferred fetch requested but neither an embedding provider nor stored embeddings are attached");
     LM_HIP(hipSetDevice(ix->device));
@@ -717,19 +705,8 @@ static int pq_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
         LM_HIP(hipStreamSynchronize(st));
         return LM_OK;
     }
-    const float* d_q = d_x;
-    if (ix->D != ix->Dp) {
-        if (n > ix->qpad_cap) {
-            if (ix->d_qpad) (void)hipFree(ix->d_qpad);
-            ix->d_qpad = nullptr;
-            ix->qpad_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_qpad, (size_t)n * ix->Dp * sizeof(float)));
-            ix->qpad_cap = n;
-        }
-        int64_t tot = n * ix->Dp;
-        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_x, n, ix->D, ix->Dp, ix->d_qpad);
-        d_q = ix->d_qpad;
-    }
+    const float* d_q = nullptr;
+    if (int prc = pad_queries(ix, n, d_x, &d_q)) return prc;
     int64_t maxb = 4096;
     int64_t nwbytes = ((ix->N + 31) / 32) * 4;
     maxb = std::max<int64_t>(1, std::min<int64_t>(maxb, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));
@@ -754,7 +731,7 @@ static int pq_filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm
     if (params->complexity <= 0) LM_FAIL(LM_EINVAL, "complexity must be positive");
     if (params->recompute_neighbors)
         LM_FAIL(LM_EINVAL, "recompute_neighbors != 0 is not supported: the traversal runs on PQ distances only, as the reference runs it (diskann_backend.py:444-451)");
-    if (!ix->d_pq_codes) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
+    if (!ix->d_pq_codes.get()) LM_FAIL(LM_ESTATE, "no PQ codes attached (lm_pq_attach)");
     if (params->use_deferred_fetch && !ix->provider && !ix->d_table)
         LM_FAIL(LM_ESTATE, "deferred fetch requested but neither an embedding provider nor stored embeddings are attached");
     if (n == 0 || ix->N == 0 || ix->entry_point < 0) return LM_OK;
@@ -784,26 +761,10 @@ int lm_pq_batch_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t
     if (n == 0) return pq_search_device(ix, 0, nullptr, k, params, nullptr, nullptr, &flt);  // the stats of an empty call
     if (!x || !labels || !distances) LM_FAIL(LM_EINVAL, "NULL buffer");
     LM_HIP(hipSetDevice(ix->device));
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
-    if (allow) {  // (lm_index_search_filtered's buffer: one allow-list per call, whichever graph search it is for)
-        if (allow_bytes > ix->filter_allow_bytes) {
-            if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
-            ix->d_filter_allow = nullptr;
-            ix->filter_allow_bytes = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_filter_allow, std::max<size_t>(allow_bytes, 16)));
-            ix->filter_allow_bytes = std::max<size_t>(allow_bytes, 16);
-        }
-        flt.d_allow = ix->d_filter_allow;
-        if (allow_bytes) LM_HIP(hipMemcpyAsync(ix->d_filter_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
-    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
-    if (int rc = pq_search_device(ix, n, ix->d_stage_x, k, params, ix->d_stage_l, ix->d_stage_d, &flt)) return rc;
-    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipStreamSynchronize(ix->stream));
-    return LM_OK;
+    if (int rc = upload_allow(ix, allow, &flt.d_allow)) return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = pq_search_device(ix, n, ix->d_stage_x.get(), k, params, ix->d_stage_l.get(), ix->d_stage_d.get(), &flt)) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 int lm_pq_batch_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, const lm_pq_search_params* params,
@@ -821,24 +782,9 @@ int lm_pq_batch_search(lm_index* ix, int64_t n, const float* x, int32_t k, const
     if (n == 0) return LM_OK;
     if (!x || !labels || !distances) LM_FAIL(LM_EINVAL, "NULL buffer");
     LM_HIP(hipSetDevice(ix->device));
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    float* d_x = ix->d_stage_x;
-    float* d_d = ix->d_stage_d;
-    int64_t* d_l = ix->d_stage_l;
-    int rc = LM_OK;
-    if (hipMemcpyAsync(d_x, x, need_x, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
-        set_error("query upload failed");
-        rc = LM_EHIP;
-    }
-    if (!rc) rc = pq_search_device(ix, n, d_x, k, params, d_l, d_d);
-    if (!rc && (hipMemcpyAsync(distances, d_d, need_d, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-                hipMemcpyAsync(labels, d_l, need_l, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-                hipStreamSynchronize(ix->stream) != hipSuccess)) {
-        set_error("result copy failed");
-        rc = LM_EHIP;
-    }
-    return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = pq_search_device(ix, n, ix->d_stage_x.get(), k, params, ix->d_stage_l.get(), ix->d_stage_d.get())) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@
 #include <hip/hip_fp16.h>
 
 #include "lm_internal.h"
+#include "lm_devbuf.h"
 
 namespace lm {
 
@@ -58,33 +59,29 @@ struct lm_index {
     int32_t D = 0, Dp = 0, metric = 0, entry_point = -1, max_level = -1;
     int32_t maxdeg0 = 0, maxdeg_up = 0;
     int64_t n_neighbors = 0, n_level_ptr = 0;
-    uint64_t* d_node_offsets = nullptr;
-    uint64_t* d_level_ptr = nullptr;
-    int32_t* d_neighbors = nullptr;
-    L0Range* d_l0 = nullptr;
+    // Device buffers of the index's own are DevBuf: grown on demand where a call needs more, freed with the index (delete, in lm_index_free).
+    DevBuf<uint64_t> d_node_offsets, d_level_ptr;
+    DevBuf<int32_t> d_neighbors;
+    DevBuf<L0Range> d_l0;
     // lm_index_create_view: the graph is the caller's level adjacencies, read in place (none of the four CSR arrays above exists)
     bool view = false;
     std::vector<lm_graph_level> view_levels;  // the descriptors as given (device pointers, borrowed)
-    ViewLevelDev* d_view_up = nullptr;        // levels 1 .. max_level for the kernel; the one device allocation a view owns for its graph
+    DevBuf<ViewLevelDev> d_view_up;           // levels 1 .. max_level for the kernel; the one device allocation a view owns for its graph
     // PQ (DiskANN-style path)
     int32_t pq_m = 0;
-    float* d_pq_codebooks = nullptr;
-    uint8_t* d_pq_codes = nullptr;
-    int32_t* d_pq_chunk_off = nullptr;
-    // lm_index_search (host pointers): query / result staging, grown on demand, freed with the index
-    float* d_stage_x = nullptr;
-    float* d_stage_d = nullptr;
-    int64_t* d_stage_l = nullptr;
-    size_t stage_x_bytes = 0, stage_d_bytes = 0, stage_l_bytes = 0;
-    unsigned long long* d_pq_nadc = nullptr;
-    int32_t* d_pq_rounds = nullptr;
-    int64_t pq_cap = 0;
-    float* d_lut = nullptr;  // two-level search: B x m x 256
-    unsigned long long* d_tstamp = nullptr;  // profiling: 2 x B stamps + [2] accumulator at the end
-    int64_t tstamp_cap = 0;
+    DevBuf<float> d_pq_codebooks;
+    DevBuf<uint8_t> d_pq_codes;
+    DevBuf<int32_t> d_pq_chunk_off;
+    // the host-pointer entry points (stage_in / stage_out): query / result staging
+    DevBuf<float> d_stage_x, d_stage_d;
+    DevBuf<int64_t> d_stage_l;
+    DevBuf<uint32_t> d_allow;  // ... and the uploaded allow-list, (N + 31) / 32 words: one per call, whichever search it is for (upload_allow)
+    DevBuf<unsigned long long> d_pq_nadc;  // per query (ensure_pq_counters)
+    DevBuf<int32_t> d_pq_rounds;
+    DevBuf<float> d_lut;  // two-level search: B x m x 256
+    DevBuf<unsigned long long> d_tstamp;  // profiling: 2 x cap stamps + [2] accumulator at the end (capacity = 2 cap + 2)
     double span_ms = 0;
     int64_t span_launches = 0;
-    int64_t lut_cap = 0;
     // stored embeddings
     void* d_table = nullptr;
     bool table_owned = false;
@@ -101,27 +98,17 @@ struct lm_index {
     int single_query_direct = 0;  // option "single_query_direct": a one-query recompute pass hands its new-list to the provider as it is (no k_uniq_*)
     int speculate = 0;            // option "speculate": candidates whose neighbours a small-batch round embeds ahead of time (k_speculate); 0 = off
     int speculate_max_batch = 2;  // option "speculate_max_batch": ... for calls of at most this many queries (larger rounds are not launch bound)
-    int32_t* d_memo_slot = nullptr;
-    float* d_memo = nullptr;
+    DevBuf<int32_t> d_memo_slot;  // N
+    float* d_memo = nullptr;      // (grows with its first rows kept: ensure_memo_rows)
     int64_t memo_cap = 0;
     int64_t memo_initial_rows = 0;  // option "memo_initial_rows": first allocation of the per-call memo (0 = max(65536, 1024 per query)); it doubles on demand up to N rows
-    int32_t* d_hub_slot_init = nullptr;  // N: slot of every hub node, -1 elsewhere (hub-embedding cache)
+    DevBuf<int32_t> d_hub_slot_init;  // N: slot of every hub node, -1 elsewhere (hub-embedding cache)
     int64_t hub_n = 0;
     std::vector<void*> ws_allocs;
-    float* d_qpad = nullptr;
-    int64_t qpad_cap = 0;
-    // lm_index_search_exact*: partial top-k lists and the uploaded allow-list, grown on demand, apart from the graph search's workspace
-    void* d_exact_ws = nullptr;
-    uint32_t* d_exact_allow = nullptr;
-    size_t exact_ws_bytes = 0, exact_allow_bytes = 0;
-    // lm_pq_flat_search*: the scan's partial lists and the uploaded allow-list, grown on demand, apart from the other paths' workspaces
-    void* d_pqflat_ws = nullptr;
-    uint32_t* d_pqflat_allow = nullptr;
-    size_t pqflat_ws_bytes = 0, pqflat_allow_bytes = 0;
-    // lm_index_search_filtered*: the per-pass result lists and per-query counts, and the uploaded allow-list, grown on demand, apart from the other paths' workspaces
-    void* d_filter_ws = nullptr;
-    uint32_t* d_filter_allow = nullptr;
-    size_t filter_ws_bytes = 0, filter_allow_bytes = 0;
+    DevBuf<float> d_qpad;  // queries padded to Dp (pad_queries)
+    // workspaces in bytes, apart from the graph search's: lm_index_search_exact*'s partial top-k lists, lm_pq_flat_search*'s partial lists,
+    // lm_index_search_filtered*'s per-pass result lists and per-query counts
+    DevBuf<unsigned char> d_exact_ws, d_pqflat_ws, d_filter_ws;
     int64_t filtered_allowed_evals = 0;  // option "filtered_allowed_evals" (read only): (query, node) pairs of the last filtered call that passed the allow test
     std::vector<int32_t> h_pq_chunk_off;  // host copy of d_pq_chunk_off (m + 1)
     unsigned long long* h_counters = nullptr;  // pinned
@@ -218,6 +205,55 @@ static int ensure_memo_rows(lm_index* ix, int64_t need, int64_t keep) {
     return LM_OK;
 }
 
+// per-query counters of the persistent kernels (k_search_table's rounds, k_pq_traverse's ADC count and rounds)
+static int ensure_pq_counters(lm_index* ix, int32_t B) {
+    if (int rc = ix->d_pq_nadc.reserve((size_t)B)) return rc;
+    return ix->d_pq_rounds.reserve((size_t)B);
+}
+
+// queries [n][D] on the device -> what the kernels read, [n][Dp]: the caller's rows where D == Dp, else a zero-padded copy in the index's buffer
+static int pad_queries(lm_index* ix, int64_t n, const float* d_x, const float** d_q) {
+    *d_q = d_x;
+    if (ix->D == ix->Dp) return LM_OK;
+    const int64_t tot = n * ix->Dp;
+    if (int rc = ix->d_qpad.reserve((size_t)tot)) return rc;
+    hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, ix->stream, d_x, n, ix->D, ix->Dp, ix->d_qpad.get());
+    *d_q = ix->d_qpad.get();
+    return LM_OK;
+}
+
+// The host-pointer entry points.  Their buffers live with the index and only ever grow -- LEANN's real call is one query at a time
+// (leann/api.py:644-796), three hipMalloc / hipFree pairs per call were a measurable part of its latency.  Calls on one index are serial and
+// each call uploads what it reads before its first launch on the index's stream: that is what lets every entry point share them.
+
+// the caller's allow-list ((N + 31) / 32 words; NULL = every node: no buffer, *d_allow = NULL) onto the device
+static int upload_allow(lm_index* ix, const uint32_t* allow, const uint32_t** d_allow) {
+    *d_allow = nullptr;
+    if (!allow) return LM_OK;
+    const size_t words = (size_t)((ix->N + 31) / 32);
+    if (int rc = ix->d_allow.reserve(words, 4)) return rc;
+    if (words) LM_HIP(hipMemcpyAsync(ix->d_allow.get(), allow, words * 4, hipMemcpyHostToDevice, ix->stream));
+    *d_allow = ix->d_allow.get();
+    return LM_OK;
+}
+
+// room for n queries and their n x k results (4096 bytes each at the least), and the queries' upload
+static int stage_in(lm_index* ix, const float* x, int64_t n, int32_t k) {
+    if (int rc = ix->d_stage_x.reserve((size_t)n * ix->D, 1024)) return rc;
+    if (int rc = ix->d_stage_d.reserve((size_t)n * k, 1024)) return rc;
+    if (int rc = ix->d_stage_l.reserve((size_t)n * k, 512)) return rc;
+    LM_HIP(hipMemcpyAsync(ix->d_stage_x.get(), x, (size_t)n * ix->D * 4, hipMemcpyHostToDevice, ix->stream));
+    return LM_OK;
+}
+
+// the staged results to the caller, and the call's last synchronisation
+static int stage_out(lm_index* ix, float* distances, int64_t* labels, int64_t n, int32_t k) {
+    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d.get(), (size_t)n * k * 4, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l.get(), (size_t)n * k * 8, hipMemcpyDeviceToHost, ix->stream));
+    LM_HIP(hipStreamSynchronize(ix->stream));
+    return LM_OK;
+}
+
 static hipEvent_t get_event(lm_index* ix) {
     hipEvent_t e;
     if (!ix->ev_pool.empty()) {
@@ -308,15 +344,8 @@ struct FilterPass {
 // the filtered search's result lists res[B][k], list lengths and per-query counts (+ their sum) in one allocation of the index's own
 static int ensure_filter_ws(lm_index* ix, int32_t B, int32_t k, FilterDev& f) {
     const size_t res_bytes = (size_t)B * k * 8, cnt_bytes = ((size_t)B + 1) * 8, len_bytes = (size_t)B * 4;
-    const size_t need = res_bytes + cnt_bytes + len_bytes;
-    if (need > ix->filter_ws_bytes) {
-        if (ix->d_filter_ws) (void)hipFree(ix->d_filter_ws);
-        ix->d_filter_ws = nullptr;
-        ix->filter_ws_bytes = 0;
-        LM_HIP(hipMalloc(&ix->d_filter_ws, need));
-        ix->filter_ws_bytes = need;
-    }
-    unsigned char* p = (unsigned char*)ix->d_filter_ws;
+    if (int rc = ix->d_filter_ws.reserve(res_bytes + cnt_bytes + len_bytes)) return rc;
+    unsigned char* p = ix->d_filter_ws.get();
     f.res = (uint64_t*)p;
     f.nallow = (unsigned long long*)(p + res_bytes);
     f.nres = (int32_t*)(p + res_bytes + cnt_bytes);
@@ -411,20 +440,11 @@ static int search_pass_persistent(lm_index* ix, int32_t B, const float* d_q, int
     ws.batch = 0;
     ws.check_rel = prm.check_relative_distance;
     hipStream_t st = ix->stream;
-    if ((int64_t)B > ix->pq_cap) {
-        if (ix->d_pq_nadc) (void)hipFree(ix->d_pq_nadc);
-        if (ix->d_pq_rounds) (void)hipFree(ix->d_pq_rounds);
-        ix->d_pq_nadc = nullptr;
-        ix->d_pq_rounds = nullptr;
-        ix->pq_cap = 0;
-        LM_HIP(hipMalloc((void**)&ix->d_pq_nadc, (size_t)B * 8));
-        LM_HIP(hipMalloc((void**)&ix->d_pq_rounds, (size_t)B * 4));
-        ix->pq_cap = B;
-    }
+    if ((rc = ensure_pq_counters(ix, B)) != LM_OK) return rc;
     PersistArgs a{};
     a.Q = d_q; a.E = ix->d_table; a.check_rel = prm.check_relative_distance; a.max_level = ix->max_level;
     a.Pmax = next_pow2(ws.maxnew); a.k = k; a.metric = ix->metric; a.labels = d_labels; a.dist = d_dist;
-    a.rounds_q = ix->d_pq_rounds;
+    a.rounds_q = ix->d_pq_rounds.get();
     const size_t shmem = ((size_t)2 * ef + a.Pmax) * 8 + (size_t)ws.maxnew * 4;
     if (shmem > 150 * 1024) {
         if (ix->view) LM_FAIL(LM_EINVAL, VIEW_LDS_TEXT);  // (view_checks refuses this before anything is staged; there is no lock-step form of a view)
@@ -439,13 +459,13 @@ static int search_pass_persistent(lm_index* ix, int32_t B, const float* d_q, int
             return l2 ? (f16 ? launch_persist_nch<true, true>(ix, a, g, shmem) : launch_persist_nch<true, false>(ix, a, g, shmem))
                       : (f16 ? launch_persist_nch<false, true>(ix, a, g, shmem) : launch_persist_nch<false, false>(ix, a, g, shmem));
         };
-        if (ix->view) rc = go(ViewDev{ix->N, ix->entry_point, ix->max_level, ix->view_levels[0].d_adj, ix->view_levels[0].cap, ix->d_view_up});
-        else rc = go(GraphDev{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets, ix->d_level_ptr, ix->d_neighbors, ix->d_l0});
+        if (ix->view) rc = go(ViewDev{ix->N, ix->entry_point, ix->max_level, ix->view_levels[0].d_adj, ix->view_levels[0].cap, ix->d_view_up.get()});
+        else rc = go(GraphDev{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets.get(), ix->d_level_ptr.get(), ix->d_neighbors.get(), ix->d_l0.get()});
     }
     if (rc) return rc;
     ix->stats.update_launches++;
     hipLaunchKernelGGL(k_stats, dim3(1), dim3(256), 0, st, ws);
-    hipLaunchKernelGGL(k_rounds_max, dim3(1), dim3(256), 0, st, ws, ix->d_pq_rounds);
+    hipLaunchKernelGGL(k_rounds_max, dim3(1), dim3(256), 0, st, ws, ix->d_pq_rounds.get());
     unsigned long long* hc = ix->h_counters;
     LM_HIP(hipMemcpyAsync(hc, ws.counters, C_NCOUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     LM_HIP(hipStreamSynchronize(st));
@@ -463,7 +483,7 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     const int32_t W = std::max(prm.beam_size, 1);
     const bool prune = prm.pq_pruning_ratio > 0.0f;
     if (prune) {
-        if (!ix->d_pq_codes) LM_FAIL(LM_ESTATE, "pq_pruning_ratio > 0 needs a product quantiser (lm_pq_attach)");
+        if (!ix->d_pq_codes.get()) LM_FAIL(LM_ESTATE, "pq_pruning_ratio > 0 needs a product quantiser (lm_pq_attach)");
         if (prm.pq_pruning_ratio >= 1.0f) LM_FAIL(LM_EINVAL, "pq_pruning_ratio must be < 1");
     }
     const bool recompute = prm.recompute != 0;
@@ -480,16 +500,9 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     PruneArgs pa{};
     size_t prune_shmem = 0;
     if (prune) {
-        const int64_t need = (int64_t)B * ix->pq_m * 256;
-        if (need > ix->lut_cap) {
-            if (ix->d_lut) (void)hipFree(ix->d_lut);
-            ix->d_lut = nullptr;
-            ix->lut_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_lut, (size_t)need * 4));
-            ix->lut_cap = need;
-        }
-        pa.Q = d_q; pa.lut = ix->d_lut; pa.codebooks = ix->d_pq_codebooks; pa.codes = ix->d_pq_codes;
-        pa.Dp = ix->Dp; pa.metric = ix->metric; pa.m = ix->pq_m; pa.chunk_off = ix->d_pq_chunk_off;
+        if ((rc = ix->d_lut.reserve((size_t)B * ix->pq_m * 256)) != LM_OK) return rc;
+        pa.Q = d_q; pa.lut = ix->d_lut.get(); pa.codebooks = ix->d_pq_codebooks.get(); pa.codes = ix->d_pq_codes.get();
+        pa.Dp = ix->Dp; pa.metric = ix->metric; pa.m = ix->pq_m; pa.chunk_off = ix->d_pq_chunk_off.get();
         pa.keep = 1.0f - prm.pq_pruning_ratio;
         pa.strategy = prm.local_prune ? 1 : (prm.send_neigh_times_ratio > 1e-6f ? 2 : 0);  // hnsw_backend.py:222-231
         pa.Pmax = next_pow2(ws.maxnew);
@@ -503,19 +516,19 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     const bool memo = memo_call || hub;                                       // rows are addressed through memo_slot
     int64_t memo_used = 0;
     if (memo) {
-        if (!ix->d_memo_slot) LM_HIP(hipMalloc((void**)&ix->d_memo_slot, (size_t)ix->N * 4));
+        if ((rc = ix->d_memo_slot.reserve((size_t)ix->N)) != LM_OK) return rc;
         const int64_t first = ix->memo_initial_rows > 0 ? ix->memo_initial_rows : std::max<int64_t>(65536, (int64_t)B * 1024);
         if ((rc = ensure_memo_rows(ix, std::min<int64_t>(ix->N, ix->hub_n + (memo_call ? first : 0)), hub ? ix->hub_n : 0)) != LM_OK) return rc;
-        ws.memo_slot = ix->d_memo_slot;
+        ws.memo_slot = ix->d_memo_slot.get();
         ws.memo = ix->d_memo;
         if (hub) {
-            LM_HIP(hipMemcpyAsync(ix->d_memo_slot, ix->d_hub_slot_init, (size_t)ix->N * 4, hipMemcpyDeviceToDevice, st));
+            LM_HIP(hipMemcpyAsync(ix->d_memo_slot.get(), ix->d_hub_slot_init.get(), (size_t)ix->N * 4, hipMemcpyDeviceToDevice, st));
             memo_used = ix->hub_n;
         } else {
-            LM_HIP(hipMemsetAsync(ix->d_memo_slot, 0xFF, (size_t)ix->N * 4, st));
+            LM_HIP(hipMemsetAsync(ix->d_memo_slot.get(), 0xFF, (size_t)ix->N * 4, st));
         }
     }
-    GraphDev g{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets, ix->d_level_ptr, ix->d_neighbors, ix->d_l0};
+    GraphDev g{ix->N, ix->entry_point, ix->max_level, ix->d_node_offsets.get(), ix->d_level_ptr.get(), ix->d_neighbors.get(), ix->d_l0.get()};
     // A ONE-query pass without a memo needs no cross-query dedup: a new-list holds every node once (visited test-and-set; an upper-level
     // list is one neighbour list), so it IS the provider's id list, in discovery order instead of id order -- three launches per round
     // fewer (the live-flag memset, k_uniq_count, k_uniq_emit).  Same labels, distances and counts (a chunk's embedding does not depend on
@@ -535,16 +548,10 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     UpdateArgs ua{};
     unsigned long long* span_acc = nullptr;
     if (ix->profiling) {
-        if (ix->tstamp_cap < B) {
-            if (ix->d_tstamp) (void)hipFree(ix->d_tstamp);
-            ix->d_tstamp = nullptr;
-            ix->tstamp_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_tstamp, ((size_t)2 * B + 2) * 8));
-            ix->tstamp_cap = B;
-        }
-        ua.tstamp = ix->d_tstamp;
-        span_acc = ix->d_tstamp + (size_t)2 * ix->tstamp_cap;
-        LM_HIP(hipMemsetAsync(ix->d_tstamp, 0, ((size_t)2 * ix->tstamp_cap + 2) * 8, st));
+        if ((rc = ix->d_tstamp.reserve((size_t)2 * B + 2)) != LM_OK) return rc;
+        ua.tstamp = ix->d_tstamp.get();
+        span_acc = ix->d_tstamp.get() + ix->d_tstamp.capacity() - 2;  // behind the stamps of the LARGEST batch so far, not of this one
+        LM_HIP(hipMemsetAsync(ix->d_tstamp.get(), 0, ix->d_tstamp.capacity() * 8, st));
     }
     ua.Q = d_q;
     ua.check_rel = prm.check_relative_distance;
@@ -628,7 +635,7 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
         if (hub && !memo_call && recompute && hc[C_NUNIQ] > 0)
             hipLaunchKernelGGL(k_memo_release, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)hc[C_NUNIQ] + 255) / 256)), dim3(256), 0, st, ws,
                                (int32_t)hc[C_NUNIQ]);
-        if (span_acc) hipLaunchKernelGGL(k_span, dim3(1), dim3(256), 0, st, ix->d_tstamp, B, span_acc);
+        if (span_acc) hipLaunchKernelGGL(k_span, dim3(1), dim3(256), 0, st, ix->d_tstamp.get(), B, span_acc);
         ix->stats.update_launches++;
     }
     if (flt) {
@@ -662,24 +669,6 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     return LM_OK;
 }
 
-// Query / result staging of the host-pointer entry points (lm_index_search, lm_pq_batch_search): the buffers live with the index and only
-// ever grow -- LEANN's real call is one query at a time (leann/api.py:644-796), three hipMalloc / hipFree pairs per call were a
-// measurable part of its latency.
-static int ensure_stage(lm_index* ix, size_t need_x, size_t need_d, size_t need_l) {
-    if (need_x <= ix->stage_x_bytes && need_d <= ix->stage_d_bytes && need_l <= ix->stage_l_bytes) return LM_OK;
-    if (ix->d_stage_x) (void)hipFree(ix->d_stage_x);
-    if (ix->d_stage_d) (void)hipFree(ix->d_stage_d);
-    if (ix->d_stage_l) (void)hipFree(ix->d_stage_l);
-    ix->d_stage_x = nullptr; ix->d_stage_d = nullptr; ix->d_stage_l = nullptr;
-    ix->stage_x_bytes = ix->stage_d_bytes = ix->stage_l_bytes = 0;
-    const size_t gx = std::max(need_x, (size_t)4096), gd = std::max(need_d, (size_t)4096), gl = std::max(need_l, (size_t)4096);
-    if (hipMalloc((void**)&ix->d_stage_x, gx) != hipSuccess || hipMalloc((void**)&ix->d_stage_d, gd) != hipSuccess ||
-        hipMalloc((void**)&ix->d_stage_l, gl) != hipSuccess)
-        LM_FAIL(LM_EHIP, "out of device memory for the query / result staging buffers");
-    ix->stage_x_bytes = gx; ix->stage_d_bytes = gd; ix->stage_l_bytes = gl;
-    return LM_OK;
-}
-
 // flt != NULL: lm_index_search_filtered* (the lock-step rounds with k_filter_collect); NULL: the launches are exactly those of the unfiltered search
 static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, float* d_dist, int64_t* d_labels,
                             const lm_search_params* params, const FilterPass* flt = nullptr) {
@@ -709,20 +698,8 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     } else if (!ix->d_table) {
         LM_FAIL(LM_ESTATE, "index stores no embeddings (pruned): recompute is required");
     }
-    // pad queries to Dp if needed
-    const float* d_q = d_x;
-    if (ix->D != ix->Dp) {
-        if (n > ix->qpad_cap) {
-            if (ix->d_qpad) (void)hipFree(ix->d_qpad);
-            ix->d_qpad = nullptr;
-            ix->qpad_cap = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_qpad, (size_t)n * ix->Dp * sizeof(float)));
-            ix->qpad_cap = n;
-        }
-        int64_t tot = n * ix->Dp;
-        hipLaunchKernelGGL(k_pad_rows, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, d_x, n, ix->D, ix->Dp, ix->d_qpad);
-        d_q = ix->d_qpad;
-    }
+    const float* d_q = nullptr;
+    if (int prc = pad_queries(ix, n, d_x, &d_q)) return prc;
     int64_t maxb = prm.max_batch > 0 ? prm.max_batch : 4096;
     // bound the visited bitmaps to 8 GiB
     int64_t nwbytes = ((ix->N + 31) / 32) * 4;
@@ -844,15 +821,16 @@ int lm_index_create_from_csr(int64_t ntotal, int32_t d, int32_t metric, const ui
     if (ntotal > 0) {
         std::vector<L0Range> l0;
         compute_degrees(ix, node_offsets, level_ptr, l0);
-        hipError_t e;
-        if ((e = hipMalloc((void**)&ix->d_l0, (size_t)ntotal * sizeof(L0Range))) != hipSuccess ||
-            (e = hipMemcpy(ix->d_l0, l0.data(), (size_t)ntotal * sizeof(L0Range), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMalloc((void**)&ix->d_node_offsets, (size_t)(ntotal + 1) * 8)) != hipSuccess ||
-            (e = hipMalloc((void**)&ix->d_level_ptr, (size_t)std::max<int64_t>(n_level_ptr, 1) * 8)) != hipSuccess ||
-            (e = hipMalloc((void**)&ix->d_neighbors, (size_t)std::max<int64_t>(n_neighbors, 1) * 4)) != hipSuccess ||
-            (e = hipMemcpy(ix->d_node_offsets, node_offsets, (size_t)(ntotal + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(ix->d_level_ptr, level_ptr, (size_t)n_level_ptr * 8, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(ix->d_neighbors, neighbors, (size_t)n_neighbors * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+        hipError_t e = hipSuccess;
+        if (ix->d_l0.reserve((size_t)ntotal) || ix->d_node_offsets.reserve((size_t)ntotal + 1) || ix->d_level_ptr.reserve((size_t)n_level_ptr) ||
+            ix->d_neighbors.reserve((size_t)n_neighbors)) {  // (the error is set)
+            lm_index_free(ix);
+            return LM_EHIP;
+        }
+        if ((e = hipMemcpy(ix->d_l0.get(), l0.data(), (size_t)ntotal * sizeof(L0Range), hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy(ix->d_node_offsets.get(), node_offsets, (size_t)(ntotal + 1) * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy(ix->d_level_ptr.get(), level_ptr, (size_t)n_level_ptr * 8, hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemcpy(ix->d_neighbors.get(), neighbors, (size_t)n_neighbors * 4, hipMemcpyHostToDevice)) != hipSuccess) {
             set_error(std::string("graph upload failed: ") + hipGetErrorString(e));
             lm_index_free(ix);
             return LM_EHIP;
@@ -932,8 +910,11 @@ int lm_index_create_view(int64_t ntotal, int32_t d, int32_t metric, const lm_gra
     std::vector<ViewLevelDev> up;
     for (int32_t l = 1; l < n_levels; ++l) up.push_back(ViewLevelDev{levels[l].d_nodes, levels[l].d_adj, (int32_t)levels[l].n_rows, levels[l].cap});
     hipError_t e = hipSuccess;
-    if (!up.empty() && ((e = hipMalloc((void**)&ix->d_view_up, up.size() * sizeof(ViewLevelDev))) != hipSuccess ||
-                        (e = hipMemcpy(ix->d_view_up, up.data(), up.size() * sizeof(ViewLevelDev), hipMemcpyHostToDevice)) != hipSuccess)) {
+    if (!up.empty() && ix->d_view_up.reserve(up.size())) {  // (the error is set)
+        lm_index_free(ix);
+        return LM_EHIP;
+    }
+    if (!up.empty() && (e = hipMemcpy(ix->d_view_up.get(), up.data(), up.size() * sizeof(ViewLevelDev), hipMemcpyHostToDevice)) != hipSuccess) {
         set_error(std::string("level descriptor upload failed: ") + hipGetErrorString(e));
         lm_index_free(ix);
         return LM_EHIP;
@@ -952,38 +933,14 @@ void lm_index_free(lm_index* ix) {
     if (!ix) return;
     (void)hipSetDevice(ix->device);
     free_ws(ix);
-    if (ix->d_node_offsets) (void)hipFree(ix->d_node_offsets);
-    if (ix->d_level_ptr) (void)hipFree(ix->d_level_ptr);
-    if (ix->d_neighbors) (void)hipFree(ix->d_neighbors);
-    if (ix->d_l0) (void)hipFree(ix->d_l0);
-    if (ix->d_view_up) (void)hipFree(ix->d_view_up);  // a view's level arrays themselves are the caller's
-    if (ix->d_memo_slot) (void)hipFree(ix->d_memo_slot);
-    if (ix->d_memo) (void)hipFree(ix->d_memo);
-    if (ix->d_hub_slot_init) (void)hipFree(ix->d_hub_slot_init);
-    if (ix->d_pq_codebooks) (void)hipFree(ix->d_pq_codebooks);
-    if (ix->d_pq_codes) (void)hipFree(ix->d_pq_codes);
-    if (ix->d_pq_chunk_off) (void)hipFree(ix->d_pq_chunk_off);
-    if (ix->d_stage_x) (void)hipFree(ix->d_stage_x);
-    if (ix->d_stage_d) (void)hipFree(ix->d_stage_d);
-    if (ix->d_stage_l) (void)hipFree(ix->d_stage_l);
-    if (ix->d_pq_nadc) (void)hipFree(ix->d_pq_nadc);
-    if (ix->d_pq_rounds) (void)hipFree(ix->d_pq_rounds);
-    if (ix->d_lut) (void)hipFree(ix->d_lut);
-    if (ix->d_tstamp) (void)hipFree(ix->d_tstamp);
+    if (ix->d_memo) (void)hipFree(ix->d_memo);  // the two device buffers that are no DevBuf: the memo, and the table where it is not borrowed
     if (ix->d_table && ix->table_owned) (void)hipFree(ix->d_table);
-    if (ix->d_qpad) (void)hipFree(ix->d_qpad);
-    if (ix->d_exact_ws) (void)hipFree(ix->d_exact_ws);
-    if (ix->d_exact_allow) (void)hipFree(ix->d_exact_allow);
-    if (ix->d_pqflat_ws) (void)hipFree(ix->d_pqflat_ws);
-    if (ix->d_pqflat_allow) (void)hipFree(ix->d_pqflat_allow);
-    if (ix->d_filter_ws) (void)hipFree(ix->d_filter_ws);
-    if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
-    if (ix->h_counters) (void)hipHostFree(ix->h_counters);
     (void)drain_events(ix, ix->ev_update);
     (void)drain_events(ix, ix->ev_expand);
     (void)drain_events(ix, ix->ev_provider);
     for (hipEvent_t e : ix->ev_pool) (void)hipEventDestroy(e);
-    delete ix;
+    if (ix->h_counters) (void)hipHostFree(ix->h_counters);
+    delete ix;  // every DevBuf (a view's level arrays themselves are the caller's)
 }
 
 int lm_index_info(const lm_index* ix, lm_index_info_t* o) {
@@ -1049,8 +1006,8 @@ int lm_index_set_hub_cache(lm_index* ix, const int32_t* ids, int32_t n, const fl
         slot[ids[i]] = i;
     }
     if (int mrc = ensure_memo_rows(ix, n, 0)) return mrc;
-    if (!ix->d_hub_slot_init) LM_HIP(hipMalloc((void**)&ix->d_hub_slot_init, (size_t)ix->N * 4));
-    LM_HIP(hipMemcpy(ix->d_hub_slot_init, slot.data(), (size_t)ix->N * 4, hipMemcpyHostToDevice));
+    if (int hrc = ix->d_hub_slot_init.reserve((size_t)ix->N)) return hrc;
+    LM_HIP(hipMemcpy(ix->d_hub_slot_init.get(), slot.data(), (size_t)ix->N * 4, hipMemcpyHostToDevice));
     LM_HIP(hipMemcpy(ix->d_memo, d_embeddings, (size_t)n * ix->Dp * 4, hipMemcpyDeviceToDevice));
     ix->hub_n = n;
     return LM_OK;
@@ -1209,24 +1166,9 @@ int lm_index_search(lm_index* ix, int64_t n, const float* x, int32_t k, float* d
     if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
     if (int vrc = view_checks(ix, n, k, params)) return vrc;
     LM_HIP(hipSetDevice(ix->device));
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    float* d_x = ix->d_stage_x;
-    float* d_d = ix->d_stage_d;
-    int64_t* d_l = ix->d_stage_l;
-    int rc = LM_OK;
-    if (hipMemcpyAsync(d_x, x, need_x, hipMemcpyHostToDevice, ix->stream) != hipSuccess) {
-        set_error("query upload failed");
-        rc = LM_EHIP;
-    }
-    if (!rc) rc = do_search_device(ix, n, d_x, k, d_d, d_l, params);
-    if (!rc && (hipMemcpyAsync(distances, d_d, need_d, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-                hipMemcpyAsync(labels, d_l, need_l, hipMemcpyDeviceToHost, ix->stream) != hipSuccess ||
-                hipStreamSynchronize(ix->stream) != hipSuccess)) {
-        set_error("result copy failed");
-        rc = LM_EHIP;
-    }
-    return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = do_search_device(ix, n, ix->d_stage_x.get(), k, ix->d_stage_d.get(), ix->d_stage_l.get(), params)) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 // Everything lm_index_search_filtered* rejects, in front of any staging or launch (do_search_device repeats the argument checks; the order --
@@ -1263,26 +1205,10 @@ int lm_index_search_filtered(lm_index* ix, int64_t n, const float* x, int32_t k,
     if (n == 0) return do_search_device(ix, 0, nullptr, k, nullptr, nullptr, params, &flt);  // the stats of an empty call
     if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
     LM_HIP(hipSetDevice(ix->device));
-    const size_t need_x = (size_t)n * ix->D * 4, need_d = (size_t)n * k * 4, need_l = (size_t)n * k * 8;
-    if (int src = ensure_stage(ix, need_x, need_d, need_l)) return src;
-    const size_t allow_bytes = (size_t)((ix->N + 31) / 32) * 4;
-    if (allow) {
-        if (allow_bytes > ix->filter_allow_bytes) {
-            if (ix->d_filter_allow) (void)hipFree(ix->d_filter_allow);
-            ix->d_filter_allow = nullptr;
-            ix->filter_allow_bytes = 0;
-            LM_HIP(hipMalloc((void**)&ix->d_filter_allow, std::max<size_t>(allow_bytes, 16)));
-            ix->filter_allow_bytes = std::max<size_t>(allow_bytes, 16);
-        }
-        flt.d_allow = ix->d_filter_allow;
-        if (allow_bytes) LM_HIP(hipMemcpyAsync(ix->d_filter_allow, allow, allow_bytes, hipMemcpyHostToDevice, ix->stream));
-    }
-    LM_HIP(hipMemcpyAsync(ix->d_stage_x, x, need_x, hipMemcpyHostToDevice, ix->stream));
-    if (int rc = do_search_device(ix, n, ix->d_stage_x, k, ix->d_stage_d, ix->d_stage_l, params, &flt)) return rc;
-    LM_HIP(hipMemcpyAsync(distances, ix->d_stage_d, need_d, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipMemcpyAsync(labels, ix->d_stage_l, need_l, hipMemcpyDeviceToHost, ix->stream));
-    LM_HIP(hipStreamSynchronize(ix->stream));
-    return LM_OK;
+    if (int rc = upload_allow(ix, allow, &flt.d_allow)) return rc;
+    if (int rc = stage_in(ix, x, n, k)) return rc;
+    if (int rc = do_search_device(ix, n, ix->d_stage_x.get(), k, ix->d_stage_d.get(), ix->d_stage_l.get(), params, &flt)) return rc;
+    return stage_out(ix, distances, labels, n, k);
 }
 
 int lm_dist_gather(const void* d_table, int32_t dtype, int32_t d_padded, int32_t metric, const float* d_q,
