@@ -350,6 +350,44 @@ size_t lm_graph_add_links_workspace_bytes(int64_t n, int64_t ne);
 int lm_graph_add_links(const void *d_table, int32_t dtype, int32_t d_padded, int32_t metric, int32_t *d_adj, float *d_dist,
                        int32_t *d_deg, int64_t n, int32_t cap, const int32_t *d_src, const int32_t *d_dst, const float *d_w, int64_t ne,
                        float alpha, void *d_workspace, size_t workspace_bytes, void *stream);
+/* Index build time: high-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3): the few nodes most lists point at keep
+ * their full lists, every other node re-selects at most m_low links, and every kept link is offered in both directions.  The reference
+ * ships graphs pruned this way (its HNSW backend's is_compact / recompute index); here it is one call, nothing returns to the host.
+ * (csrc/lm_prune_impl.h)
+ *   d_table   [n][d_padded]  fp32 or fp16 rows, zero padded (lm_graph_add_links' layout);
+ *   d_adj_in  [n][cap]       the level-0 adjacency in lm_graph_add_links' layout; read only;
+ *   d_adj_out / d_dist_out [n][cap], d_deg_out [n]   out: the pruned level, EVERY row written; buffers other than the input;
+ *   d_hubs    [n_hubs]       out, or NULL: the hubs, in the order of step 3;
+ *   d_indeg   [n]            out, or NULL: the in-degrees of step 2.
+ * The contract, per call:
+ *   1. Usable slot: slot c of row v is usable when its value u is in [0, n) and u != v.  Every other slot is empty; holes are tolerated;
+ *      duplicates within a row are taken as they are.
+ *   2. In-degree: indeg[u] = the number of usable slots, over all rows, whose value is u.
+ *   3. Hubs: H = the first n_hubs nodes under the key (indeg descending, id ascending) -- a total order: ties at the cut go to the lower id.
+ *   4. Quota: quota[v] = cap for v in H, else mq = min(m_low, cap).
+ *   5. Kept links and edges: row v keeps its first quota[v] usable slots in slot order.  With base[v] = the sum of quota[v'] over v' < v
+ *      and (v, u) the r-th kept link of v, j = base[v] + r: edge 2j is v -> u, edge 2j + 1 is u -> v, both with the weight w = the canonical
+ *      internal distance orc_dist of row v as the query and row u as the row (squared L2, or -ip; fp32, fp16 rows widened first; a NaN
+ *      result is stored as the quiet NaN 0x7FC00000: IEEE 754 leaves the sign and payload of a computed NaN to the platform).  Every
+ *      j < base[n] that no kept link fills (a row with fewer usable slots than its quota) gives two INVALID edges (src = dst = -1); nothing
+ *      is dereferenced for them.  ne = 2 * base[n] = 2 * (n_hubs * cap + (n - n_hubs) * mq): a function of the arguments alone.
+ *   6. Result: d_adj_out / d_dist_out / d_deg_out are what lm_graph_add_links leaves when it is called ONCE with these ne edges, this
+ *      alpha, cap and table on an empty graph (every slot -1, every distance +inf, every degree 0): its steps 1-6 as stated above.  Rows
+ *      that receive no valid edge stay empty with degree 0.  One call, not chunks: the result is a function of the input bits alone.
+ * No floating-point atomics (integer atomics count, nothing else); no host synchronisation, allocation or device-to-host copy: everything
+ * is enqueued on `stream`.
+ * Workspace: lm_graph_prune_hubs_workspace_bytes(n, cap, m_low, n_hubs), a pure function of its arguments that includes
+ * lm_graph_add_links_workspace_bytes(n, ne); 0 for arguments the call rejects and for n == 0.  d_workspace must be 8-byte aligned.
+ * Cost that does not depend on the graph: one 1024-lane workgroup walks all n nodes once more than lm_graph_add_links does (hub ranks and
+ * base[]); with d_hubs the hub keys are sorted by a bitonic network (one launch per step above 512 keys).
+ * LM_EINVAL (before anything is launched, the buffers untouched): whatever lm_graph_add_links rejects for dtype, d_padded, metric, cap and
+ * alpha; m_low < 1; n_hubs < 0 or > n; n < 0, n * cap > INT32_MAX or ne > INT32_MAX; a NULL d_table, d_adj_in, d_adj_out, d_dist_out,
+ * d_deg_out or d_workspace; d_adj_out == d_adj_in; a misaligned d_workspace or workspace_bytes below the function above.  n == 0: LM_OK. */
+size_t lm_graph_prune_hubs_workspace_bytes(int64_t n, int32_t cap, int32_t m_low, int64_t n_hubs);
+int lm_graph_prune_hubs(const void *d_table, int32_t dtype, int32_t d_padded, int32_t metric, const int32_t *d_adj_in, int64_t n,
+                        int32_t cap, int32_t m_low, int64_t n_hubs, float alpha, int32_t *d_adj_out, float *d_dist_out,
+                        int32_t *d_deg_out, int32_t *d_hubs /* [n_hubs] or NULL */, int32_t *d_indeg /* [n] or NULL */,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
 /* Exact top-k over a stored-embedding table = oracle/lm_oracle.c:orc_bruteforce_topk (the paper's IndexFlatIP baseline) plus an allow-list.  The
  * reference has no such path: leann/api.py:785-790 applies metadata_filters AFTER the graph search, so a filtered query returns fewer than top_k
  * hits; here the filter is part of the scan and the result is the best k of the allowed rows.  (csrc/lm_exact_impl.h)

@@ -142,7 +142,9 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         (bool, default False): both of these insert their links with the library's kernel (lm_graph_add_links) instead of torch ops.
         ``gpu_search_view`` (bool, default False): the GPU builder searches its level graphs in place through a view index
         (lm_index_create_view, build_graph_gpu(search="view")) instead of re-assembling a CSR for every insert batch; needs
-        ``gpu_link_kernel``."""
+        ``gpu_link_kernel``.  ``gpu_prune_kernel`` (bool, default False): the pruning runs as one library call on the device
+        (lm_graph_prune_hubs, prune_preserving_hubs(pruner="kernel")): in-degrees, hub choice -- ties at the cut go to the lower id --,
+        link weights and the link insertion, instead of numpy / torch ops on the host's copy of the graph."""
         from .hnsw_builder import build_hnsw
 
         bp = self.build_params
@@ -151,6 +153,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         selector = "kernel" if bool(bp.get("gpu_select_kernel", False)) else "torch"
         linker = "kernel" if bool(bp.get("gpu_link_kernel", False)) else "torch"
         search = "view" if bool(bp.get("gpu_search_view", False)) else "csr"
+        prune_kernel = bool(bp.get("gpu_prune_kernel", False))
         use_gpu = data.shape[0] >= thr and _lib.device_count() > 0
         if not use_gpu and m_low <= 0:
             return build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
@@ -163,12 +166,13 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
             g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker, search=search)
         else:
             x = torch.from_numpy(np.ascontiguousarray(data))
-            if selector == "kernel" or linker == "kernel":  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)
+            if selector == "kernel" or linker == "kernel" or (prune_kernel and m_low > 0):  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)
                 _lib.require_gpu()
                 x = x.to(torch.device("cuda", int(bp.get("device", 0))))
             g = build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
         if m_low > 0:
-            g = prune_preserving_hubs(g, x, self.M, m_low, float(bp.get("hub_fraction", 0.02)), selector=selector, linker=linker)
+            kw = {"pruner": "kernel"} if prune_kernel else {}  # (absent: prune_preserving_hubs' default, the host form)
+            g = prune_preserving_hubs(g, x, self.M, m_low, float(bp.get("hub_fraction", 0.02)), selector=selector, linker=linker, **kw)
         return g
 
 

@@ -265,21 +265,8 @@ __global__ __launch_bounds__(LINK_NT) void k_link_row(const void* table, int32_t
 
 inline size_t link_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-}  // namespace lm
-
-extern "C" {
-
-// workspace: counters / cursors [n], bucket starts [n], affected rows [n] + their number, then the buckets: dst, edge index, weight [ne] each
-size_t lm_graph_add_links_workspace_bytes(int64_t n, int64_t ne) {
-    if (n < 0 || ne < 0 || n > 0x7fffffffll || ne > 0x7fffffffll) return 0;
-    if (n == 0 || ne == 0) return 0;
-    return 2 * lm::link_align((size_t)n * 4) + lm::link_align(((size_t)n + 1) * 4) + 3 * lm::link_align((size_t)ne * 4);
-}
-
-int lm_graph_add_links(const void* d_table, int32_t dtype, int32_t d_padded, int32_t metric, int32_t* d_adj, float* d_dist, int32_t* d_deg, int64_t n,
-                       int32_t cap, const int32_t* d_src, const int32_t* d_dst, const float* d_w, int64_t ne, float alpha, void* d_workspace,
-                       size_t workspace_bytes, void* stream) {
-    using namespace lm;
+// what lm_graph_add_links and lm_graph_prune_hubs (lm_prune_impl.h) reject alike: the table's layout, the metric, cap, alpha
+inline int link_check_params(int32_t dtype, int32_t d_padded, int32_t metric, int32_t cap, float alpha) {
     if (d_padded <= 0 || d_padded % 64) LM_FAIL(LM_EINVAL, "d_padded must be a positive multiple of 64");
     switch (d_padded / 64) {
         case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 12: case 16: break;
@@ -289,11 +276,13 @@ int lm_graph_add_links(const void* d_table, int32_t dtype, int32_t d_padded, int
     if (metric != LM_METRIC_INNER_PRODUCT && metric != LM_METRIC_L2) LM_FAIL(LM_EINVAL, "unknown metric");
     if (cap < 1 || cap > LINK_MAX_CAP) LM_FAIL(LM_EINVAL, "cap must be in [1, LM_SELECT_MAX_K / 2 = " + std::to_string(LINK_MAX_CAP) + "]");
     if (!std::isfinite(alpha) || alpha < 1.0f) LM_FAIL(LM_EINVAL, "alpha must be finite and >= 1");
-    if (n < 0 || ne < 0 || n > 0x7fffffffll || ne > 0x7fffffffll) LM_FAIL(LM_EINVAL, "n / ne must be in [0, INT32_MAX]");
-    if (n == 0 || ne == 0) return LM_OK;
-    if (!d_table || !d_adj || !d_dist || !d_deg || !d_src || !d_dst || !d_w || !d_workspace) LM_FAIL(LM_EINVAL, "NULL buffer");
-    if ((uintptr_t)d_workspace % 4) LM_FAIL(LM_EINVAL, "d_workspace must be 4-byte aligned");
-    if (workspace_bytes < lm_graph_add_links_workspace_bytes(n, ne)) LM_FAIL(LM_EINVAL, "workspace smaller than lm_graph_add_links_workspace_bytes(n, ne)");
+    return LM_OK;
+}
+
+// the launch sequence of lm_graph_add_links on checked arguments (n, ne in [1, INT32_MAX], a workspace of at least
+// lm_graph_add_links_workspace_bytes(n, ne)): both entry points enqueue exactly this
+inline int link_launch(const void* d_table, int32_t dtype, int32_t d_padded, int32_t metric, int32_t* d_adj, float* d_dist, int32_t* d_deg, int64_t n, int32_t cap,
+                       const int32_t* d_src, const int32_t* d_dst, const float* d_w, int64_t ne, float alpha, void* d_workspace, hipStream_t st) {
     char* ws = (char*)d_workspace;
     int32_t* cnt = (int32_t*)ws;
     int32_t* start = (int32_t*)(ws + link_align((size_t)n * 4));
@@ -302,7 +291,6 @@ int lm_graph_add_links(const void* d_table, int32_t dtype, int32_t d_padded, int
     int32_t* b_dst = (int32_t*)bk;
     int32_t* b_e = (int32_t*)(bk + link_align((size_t)ne * 4));
     float* b_w = (float*)(bk + 2 * link_align((size_t)ne * 4));
-    hipStream_t st = (hipStream_t)stream;
     LM_HIP(hipMemsetAsync(cnt, 0, (size_t)n * 4, st));
     const dim3 egrid((unsigned)((ne + 255) / 256));
     hipLaunchKernelGGL(k_link_count, egrid, dim3(256), 0, st, d_src, d_dst, ne, n, cnt);
@@ -327,6 +315,30 @@ int lm_graph_add_links(const void* d_table, int32_t dtype, int32_t d_padded, int
 #undef LM_LINK_ARGS
     LM_HIP(hipGetLastError());
     return LM_OK;
+}
+
+}  // namespace lm
+
+extern "C" {
+
+// workspace: counters / cursors [n], bucket starts [n], affected rows [n] + their number, then the buckets: dst, edge index, weight [ne] each
+size_t lm_graph_add_links_workspace_bytes(int64_t n, int64_t ne) {
+    if (n < 0 || ne < 0 || n > 0x7fffffffll || ne > 0x7fffffffll) return 0;
+    if (n == 0 || ne == 0) return 0;
+    return 2 * lm::link_align((size_t)n * 4) + lm::link_align(((size_t)n + 1) * 4) + 3 * lm::link_align((size_t)ne * 4);
+}
+
+int lm_graph_add_links(const void* d_table, int32_t dtype, int32_t d_padded, int32_t metric, int32_t* d_adj, float* d_dist, int32_t* d_deg, int64_t n,
+                       int32_t cap, const int32_t* d_src, const int32_t* d_dst, const float* d_w, int64_t ne, float alpha, void* d_workspace,
+                       size_t workspace_bytes, void* stream) {
+    using namespace lm;
+    if (int rc = link_check_params(dtype, d_padded, metric, cap, alpha)) return rc;
+    if (n < 0 || ne < 0 || n > 0x7fffffffll || ne > 0x7fffffffll) LM_FAIL(LM_EINVAL, "n / ne must be in [0, INT32_MAX]");
+    if (n == 0 || ne == 0) return LM_OK;
+    if (!d_table || !d_adj || !d_dist || !d_deg || !d_src || !d_dst || !d_w || !d_workspace) LM_FAIL(LM_EINVAL, "NULL buffer");
+    if ((uintptr_t)d_workspace % 4) LM_FAIL(LM_EINVAL, "d_workspace must be 4-byte aligned");
+    if (workspace_bytes < lm_graph_add_links_workspace_bytes(n, ne)) LM_FAIL(LM_EINVAL, "workspace smaller than lm_graph_add_links_workspace_bytes(n, ne)");
+    return link_launch(d_table, dtype, d_padded, metric, d_adj, d_dist, d_deg, n, cap, d_src, d_dst, d_w, ne, alpha, d_workspace, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 //   lm_exact_impl.h   exact top-k over the stored table with an allow-list: k_exact_scan (row slice x query tile), k_exact_merge
 //   lm_filter_impl.h  allow-list for the graph search (lm_index_search_filtered*): k_filter_collect, once per lock-step round before k_update
 //   lm_link_impl.h    index build time: link insertion (lm_graph_add_links): k_link_count / k_link_scan / k_link_fill / k_link_row
+//   lm_prune_impl.h   index build time: hub-preserving pruning (lm_graph_prune_hubs): k_prune_indeg / k_prune_hist / k_prune_pick / k_prune_scan /
+//                     k_prune_emit / k_prune_sort_*, then lm_link_impl.h's launch sequence
 //   lm_view_impl.h    lm_index_create_view: k_search_table's dense-level graph accessor (fixed-capacity level adjacencies searched in place)
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
@@ -1255,4 +1257,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_exact_impl.h"
 #include "lm_pq_flat_impl.h"
 #include "lm_link_impl.h"
+#include "lm_prune_impl.h"
 

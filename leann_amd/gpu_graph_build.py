@@ -642,58 +642,40 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
 
 
 @torch.no_grad()
-def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch",
-                          linker: str = "torch") -> HnswCsr:
-    """High-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3, p. 6): storage drops from ~2M links per node
-    to ~m_low while the few hub nodes that most searches pass through keep their full lists.
+def prune_level0_kernel(table: torch.Tensor, adj_int32: torch.Tensor, m_low: int, n_hubs: int, metric: int, alpha: float = 1.0, return_indeg: bool = False):
+    """Algorithm 3 on the level-0 adjacency as one library call (lm_graph_prune_hubs; include/leann_mi355x.h states the contract).
+    ``table``: the embeddings, fp32 or fp16 (padded with _padded_table if they are not yet); ``adj_int32`` [n, cap]: the level-0 lists,
+    -1 padded, on the table's device.  -> (adj int32 [n, cap], dist fp32 [n, cap] internal distances, deg int32 [n], hubs int32 [n_hubs]:
+    in-degree descending, id ascending); with ``return_indeg`` a fifth: the in-degrees, int32 [n]."""
+    from . import _lib
 
-      * V* = the ``hub_fraction`` (paper: 2 %) nodes of highest degree -- in-degree here: how many lists a node appears in;
-      * every node re-selects its out-links from its candidate list W(v) in the original (heuristic) order: up to 2M (the
-        level-0 cap of the unpruned graph) for v in V*, up to ``m_low`` < M otherwise.  W(v) is v's list in the input graph:
-        the builder produced it with the select-neighbours heuristic from an ef_construction-sized candidate set, so this
-        is the paper's re-selection without repeating the N searches;
-      * for every kept link v -> u the reverse link u -> v is offered as well and every node may hold up to 2M links in
-        total, overflowing lists being shrunk with the same heuristic (paper: "all nodes establish bidirectional edges up
-        to the maximum threshold M; only the number of outgoing selections of low-degree nodes is restricted").
-    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device; ``selector`` and
-    ``linker`` as in build_graph_gpu."""
-    _selector_fn(selector)
-    _check_linker(linker)
+    lib = _lib.load()
+    tab = _padded_table(table)
+    a_in = adj_int32.to(device=tab.device, dtype=torch.int32).contiguous()
+    n, cap = a_in.shape
+    dev = tab.device
+    adj = torch.empty((n, cap), dtype=torch.int32, device=dev)
+    dist = torch.empty((n, cap), dtype=torch.float32, device=dev)
+    deg = torch.empty((n,), dtype=torch.int32, device=dev)
+    hubs = torch.empty((max(int(n_hubs), 0),), dtype=torch.int32, device=dev)
+    indeg = torch.empty((n,), dtype=torch.int32, device=dev) if return_indeg else None
+    need = int(lib.lm_graph_prune_hubs_workspace_bytes(n, cap, int(m_low), int(n_hubs)))
+    ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream if tab.is_cuda else None
+    rc = lib.lm_graph_prune_hubs(tab.data_ptr(), _lib.DTYPE_F16 if tab.dtype == torch.float16 else _lib.DTYPE_F32, tab.shape[1], int(metric), a_in.data_ptr(), n, cap,
+                                 int(m_low), int(n_hubs), float(alpha), adj.data_ptr(), dist.data_ptr(), deg.data_ptr(), hubs.data_ptr() if hubs.numel() else None,
+                                 indeg.data_ptr() if return_indeg and n else None, ws.data_ptr(), ws.numel(), stream)
+    _lib.check(rc, "lm_graph_prune_hubs")
+    return (adj, dist, deg, hubs, indeg) if return_indeg else (adj, dist, deg, hubs)
+
+
+PRUNERS = ("torch", "kernel")
+
+
+def _with_level0(g: HnswCsr, new0: np.ndarray) -> HnswCsr:
+    """``g`` with its level-0 lists replaced by the rows of ``new0`` [n, cap] (-1 = empty, left-packed or not); upper levels copied."""
     n = g.ntotal
-    if n == 0 or m_low >= 2 * M:
-        return g
-    dev = x.device
-    mt = g.metric_type
     p0 = g.node_offsets[:-1].astype(np.int64)
-    beg = g.level_ptr[p0].astype(np.int64)
-    deg = (g.level_ptr[p0 + 1].astype(np.int64) - beg)
-    cap = 2 * M
-    # dense level-0 adjacency [n, cap] in stored order (-1 padded)
-    adj = np.full((n, cap), -1, np.int64)
-    col = np.arange(cap)[None, :]
-    m = col < np.minimum(deg, cap)[:, None]
-    adj[m] = g.neighbors[(beg[:, None] + col)[m]]
-    indeg = np.bincount(adj[m], minlength=n)  # in how many level-0 lists a node appears
-    nh = max(1, int(round(hub_fraction * n)))
-    hubs = np.argpartition(-indeg, min(nh, n - 1))[:nh]
-    quota = np.full(n, m_low, np.int64)
-    quota[hubs] = cap
-    keep = (col < quota[:, None]) & (adj >= 0)
-    src = torch.from_numpy(np.broadcast_to(np.arange(n)[:, None], adj.shape)[keep].copy()).to(dev)
-    dst = torch.from_numpy(adj[keep]).to(dev)
-    # similarities of the kept links (larger = closer), in blocks
-    w = torch.empty(src.shape[0], dtype=torch.float32, device=dev)
-    for b0 in range(0, src.shape[0], 1 << 20):
-        a, b = x[src[b0 : b0 + (1 << 20)]].float(), x[dst[b0 : b0 + (1 << 20)]].float()
-        w[b0 : b0 + (1 << 20)] = (a * b).sum(1) if mt == METRIC_INNER_PRODUCT else -((a - b) ** 2).sum(1)
-    G = _LevelGraph(torch.arange(n, device=dev), cap, selector, linker)
-    xsel = _padded_table(x) if selector == "kernel" or linker == "kernel" else x
-    step = 1 << 21  # bound the temporaries of add_links
-    for b0 in range(0, src.shape[0], step):
-        s_, d_, w_ = src[b0 : b0 + step], dst[b0 : b0 + step], w[b0 : b0 + step]
-        G.add_links(xsel, torch.cat([s_, d_]), torch.cat([d_, s_]), torch.cat([w_, w_]), mt)
-    new0 = G.export()
-    # reassemble: level 0 replaced, upper levels copied
     nlev = g.levels.astype(np.int64)
     nptr = int(g.node_offsets[-1])
     old_deg = np.diff(np.concatenate([g.level_ptr.astype(np.int64), [g.neighbors.shape[0]]]))[:nptr] if nptr else np.zeros(0, np.int64)
@@ -718,8 +700,77 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
             b, e = int(g.level_ptr[p]), int(g.level_ptr[p + 1])
             nb = int(level_ptr[p])
             neighbors[nb : nb + (e - b)] = g.neighbors[b:e]
-    out = HnswCsr(d=g.d, ntotal=n, metric_type=mt, levels=g.levels.copy(), level_ptr=level_ptr, node_offsets=g.node_offsets.copy(),
+    out = HnswCsr(d=g.d, ntotal=n, metric_type=g.metric_type, levels=g.levels.copy(), level_ptr=level_ptr, node_offsets=g.node_offsets.copy(),
                   neighbors=neighbors, entry_point=g.entry_point, max_level=g.max_level, ef_construction=g.ef_construction,
                   cum_nneighbor_per_level=g.cum_nneighbor_per_level)
     out.validate()
     return out
+
+
+@torch.no_grad()
+def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch",
+                          linker: str = "torch", pruner: str = "torch", return_hubs: bool = False):
+    """High-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3, p. 6): storage drops from ~2M links per node
+    to ~m_low while the few hub nodes that most searches pass through keep their full lists.
+
+      * V* = the ``hub_fraction`` (paper: 2 %) nodes of highest degree -- in-degree here: how many lists a node appears in;
+      * every node re-selects its out-links from its candidate list W(v) in the original (heuristic) order: up to 2M (the
+        level-0 cap of the unpruned graph) for v in V*, up to ``m_low`` < M otherwise.  W(v) is v's list in the input graph:
+        the builder produced it with the select-neighbours heuristic from an ef_construction-sized candidate set, so this
+        is the paper's re-selection without repeating the N searches;
+      * for every kept link v -> u the reverse link u -> v is offered as well and every node may hold up to 2M links in
+        total, overflowing lists being shrunk with the same heuristic (paper: "all nodes establish bidirectional edges up
+        to the maximum threshold M; only the number of outgoing selections of low-degree nodes is restricted").
+    Upper levels are untouched (they hold ~N/M nodes).  Returns a new graph; ``x`` = the [N, D] embeddings on any device; ``selector`` and
+    ``linker`` as in build_graph_gpu.
+
+    ``pruner``: "torch" (default): the host form below (numpy in-degrees and hub choice, ties at the cut as np.argpartition leaves them,
+    torch link weights, add_links in chunks).  "kernel": one call of lm_graph_prune_hubs on the device (prune_level0_kernel): hubs under
+    the total order (in-degree descending, id ascending), canonical fp32 link weights, one link insertion -- the canonical rule whatever
+    ``selector`` and ``linker`` say --; the level-0 lists go up as an int32 [n, 2M] array.  ``return_hubs``: return (graph, hubs) -- the
+    hub ids as an int64 numpy array (``pruner="kernel"``: in the contract's order; an empty array when nothing was pruned)."""
+    _selector_fn(selector)
+    _check_linker(linker)
+    if pruner not in PRUNERS:
+        raise ValueError(f"pruner must be one of {PRUNERS}, not {pruner!r}")
+    n = g.ntotal
+    if n == 0 or m_low >= 2 * M:
+        return (g, np.zeros(0, np.int64)) if return_hubs else g
+    dev = x.device
+    mt = g.metric_type
+    p0 = g.node_offsets[:-1].astype(np.int64)
+    beg = g.level_ptr[p0].astype(np.int64)
+    deg = (g.level_ptr[p0 + 1].astype(np.int64) - beg)
+    cap = 2 * M
+    nh = max(1, int(round(hub_fraction * n)))
+    col = np.arange(cap)[None, :]
+    m = col < np.minimum(deg, cap)[:, None]
+    if pruner == "kernel":
+        adj32 = np.full((n, cap), -1, np.int32)
+        adj32[m] = g.neighbors[(beg[:, None] + col)[m]]
+        new32, _, _, hubs_d = prune_level0_kernel(_padded_table(x), torch.from_numpy(adj32).to(dev), m_low, nh, mt)
+        out = _with_level0(g, new32.cpu().numpy())
+        return (out, hubs_d.cpu().numpy().astype(np.int64)) if return_hubs else out
+    # dense level-0 adjacency [n, cap] in stored order (-1 padded)
+    adj = np.full((n, cap), -1, np.int64)
+    adj[m] = g.neighbors[(beg[:, None] + col)[m]]
+    indeg = np.bincount(adj[m], minlength=n)  # in how many level-0 lists a node appears
+    hubs = np.argpartition(-indeg, min(nh, n - 1))[:nh]
+    quota = np.full(n, m_low, np.int64)
+    quota[hubs] = cap
+    keep = (col < quota[:, None]) & (adj >= 0)
+    src = torch.from_numpy(np.broadcast_to(np.arange(n)[:, None], adj.shape)[keep].copy()).to(dev)
+    dst = torch.from_numpy(adj[keep]).to(dev)
+    # similarities of the kept links (larger = closer), in blocks
+    w = torch.empty(src.shape[0], dtype=torch.float32, device=dev)
+    for b0 in range(0, src.shape[0], 1 << 20):
+        a, b = x[src[b0 : b0 + (1 << 20)]].float(), x[dst[b0 : b0 + (1 << 20)]].float()
+        w[b0 : b0 + (1 << 20)] = (a * b).sum(1) if mt == METRIC_INNER_PRODUCT else -((a - b) ** 2).sum(1)
+    G = _LevelGraph(torch.arange(n, device=dev), cap, selector, linker)
+    xsel = _padded_table(x) if selector == "kernel" or linker == "kernel" else x
+    step = 1 << 21  # bound the temporaries of add_links
+    for b0 in range(0, src.shape[0], step):
+        s_, d_, w_ = src[b0 : b0 + step], dst[b0 : b0 + step], w[b0 : b0 + step]
+        G.add_links(xsel, torch.cat([s_, d_]), torch.cat([d_, s_]), torch.cat([w_, w_]), mt)
+    out = _with_level0(g, G.export())
+    return (out, hubs.astype(np.int64)) if return_hubs else out
