@@ -388,6 +388,56 @@ int lm_graph_prune_hubs(const void *d_table, int32_t dtype, int32_t d_padded, in
                         int32_t cap, int32_t m_low, int64_t n_hubs, float alpha, int32_t *d_adj_out, float *d_dist_out,
                         int32_t *d_deg_out, int32_t *d_hubs /* [n_hubs] or NULL */, int32_t *d_indeg /* [n] or NULL */,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+/* Index build time: ONE insert step of the batched HNSW builder on a view index -- search the level as it stands, form every row's
+ * candidates, select neighbours, link both directions.  The reference does all of it inside faiss' index.add
+ * (leann_backend_hnsw/hnsw_backend.py:66-94); the four calls above are its pieces, this call is the step that makes a builder of them, so
+ * that a plain-C host can build an index and the glue between the kernels has a pinned result.  (csrc/lm_insert_impl.h)
+ *   view     a handle from lm_index_create_view with a table attached (fp32 or fp16, owned or borrowed); n = its ntotal, cap = its
+ *            levels[0].cap;
+ *   d_batch  [b]        the node ids to insert (replace == 0) or to refine (replace == 1);
+ *   d_adj    [n][cap]   the very pointer the view holds as level 0; d_dist [n][cap] and d_deg [n]: that level's other two arrays, in
+ *                       lm_graph_add_links' layout;
+ *   K = kk when replace == 0, kk + cap when replace == 1;
+ *   d_cand_out / d_cdist_out / d_keep_out [b][K]   out, or NULL: the candidates of steps 3-5 and the keep mask of step 6.
+ * Everything is enqueued on the index's stream (lm_index_set_stream).  The index owns every intermediate buffer (queries, search result,
+ * candidates, keep mask, edges, the link insertion's workspace): they grow on demand and are freed with the index; a call that rejects its
+ * arguments allocates nothing.
+ * The contract, per call and for every row i of the batch, v = d_batch[i]:
+ *   1. Query: the table row of v as fp32 -- its first d values, fp16 widened exactly.  v outside [0, n): the row is VOID; its query is all
+ *      zeros, nothing is dereferenced for it, its candidates are all empty, it emits only invalid edges and clears nothing.
+ *   2. Search: S(i) = the kk (label, distance) pairs that lm_index_search_device(view, b, queries, kk, ..., params) returns for that query:
+ *      the view's own search, bit for bit, with every rule and rejection of a view search, on the level as it stands when the call begins.
+ *      The INTERNAL distance of an entry is squared L2, or the negated inner product: the exact negation of what the search decodes.
+ *   3. Candidates, replace == 0: the kk entries of S(i) in the order returned (a label outside [0, n) is empty).
+ *   4. Candidates, replace == 1: the concatenation of S(i), with every entry whose label is v (or outside [0, n)) made empty, and the cap
+ *      slots of row v of d_adj / d_dist in slot order (a slot value outside [0, n) is empty).  Dedupe by id: the first occurrence in the
+ *      concatenation survives -- a search entry beats a stored slot --, later ones become empty.  The non-empty entries are ordered by the
+ *      key (internal distance ascending, position in the concatenation ascending), -0 counting as +0; empty entries follow.  Every row is
+ *      read as it was when the call began.
+ *   5. Non-finite distances: in both modes an entry whose internal distance is not finite (+-inf, NaN) is empty.  In step 4 it is dropped
+ *      after the dedupe (it still shadows the later occurrences of its id) and before the ordering.  Empty entries have id -1 and distance
+ *      +inf; every other entry keeps the distance bits it came with.  d_cand_out / d_cdist_out receive exactly these K entries per row.
+ *   6. Selection: keep[i][.] = what lm_select_neighbors leaves for (cand, dist, K, m, alpha) on the view's table: its rule as it stands,
+ *      the strict pass, then the relaxed pass when alpha != 1.  d_keep_out receives it.
+ *   7. Edges: ne = 2 * b * m.  With (v, u, w) the r-th kept candidate of row i in candidate order (r < m): edge i * m + r is v -> u with
+ *      weight w, edge b * m + i * m + r is u -> v with weight w; every other edge index is INVALID (src = dst = -1).  The valid edges thus
+ *      come as all forward edges row-major, then all reverse edges, and lm_graph_add_links' tie rule "the lowest e wins" decides on them.
+ *   8. Clearing: when replace == 1 every non-void row v of the batch is cleared (adj -1, dist +inf, deg 0), after all candidates have been
+ *      formed and before step 9.
+ *   9. Linking: d_adj / d_dist / d_deg become what lm_graph_add_links leaves when called ONCE with these ne edges, this alpha, cap and
+ *      table: its steps 1-6 as written.  Rows that receive no valid edge and were not cleared keep every byte.
+ * Duplicate ids in d_batch are tolerated: every occurrence is processed as stated (the edges repeat and step 9 dedupes them, clearing is
+ * idempotent); the result is still a function of the input bits alone.
+ * No floating-point atomics; no host synchronisation, allocation inside the kernels, or device-to-host copy other than what the view
+ * search itself does (its one counter read per pass); lm_index_get_stats afterwards reads as after that search.
+ * Rejections, each before anything is staged or launched, all buffers untouched.  LM_EINVAL: a NULL handle, params or level array, NULL
+ * d_batch with b > 0; b < 0 or 2 * b * m > INT32_MAX; replace not 0 or 1; kk < 1, m < 1, K > LM_SELECT_MAX_K; whatever lm_graph_add_links
+ * rejects for cap and alpha; d_adj different from the view's level-0 array.  LM_ESTATE: a handle that is not a view; no table attached.
+ * Everything the view search rejects for params and k = kk comes back with the search's own code (recompute, batch_size,
+ * pq_pruning_ratio, the LDS rule, beam_size > 64, option persistent_table 0).  b == 0: LM_OK, nothing is written. */
+int lm_graph_insert_batch(lm_index *view, const int32_t *d_batch, int64_t b, int32_t replace, int32_t kk, int32_t m, float alpha,
+                          const lm_search_params *params, int32_t *d_adj, float *d_dist, int32_t *d_deg,
+                          int32_t *d_cand_out /* [b][K] or NULL */, float *d_cdist_out /* [b][K] or NULL */, uint8_t *d_keep_out /* [b][K] or NULL */);
 /* Exact top-k over a stored-embedding table = oracle/lm_oracle.c:orc_bruteforce_topk (the paper's IndexFlatIP baseline) plus an allow-list.  The
  * reference has no such path: leann/api.py:785-790 applies metadata_filters AFTER the graph search, so a filtered query returns fewer than top_k
  * hits; here the filter is part of the scan and the result is the best k of the allowed rows.  (csrc/lm_exact_impl.h)

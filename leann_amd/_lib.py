@@ -115,7 +115,7 @@ EXPORTED_SYMBOLS = [
     "lm_index_attach_table", "lm_index_set_provider", "lm_index_set_hub_cache", "lm_index_set_stream",
     "lm_search_params_default", "lm_index_search", "lm_index_search_device",
     "lm_index_get_stats", "lm_index_set_profiling", "lm_index_set_option", "lm_index_get_option", "lm_index_event_overhead_us",
-    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_graph_add_links", "lm_graph_add_links_workspace_bytes", "lm_graph_prune_hubs", "lm_graph_prune_hubs_workspace_bytes", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
+    "lm_dist_gather", "lm_topk_merge", "lm_select_neighbors", "lm_graph_add_links", "lm_graph_add_links_workspace_bytes", "lm_graph_prune_hubs", "lm_graph_prune_hubs_workspace_bytes", "lm_graph_insert_batch", "lm_pq_encode", "lm_pq_train", "lm_pq_train_workspace_bytes",
     "lm_exact_search", "lm_exact_search_workspace_bytes", "lm_index_search_exact", "lm_index_search_exact_device",
     "lm_index_search_filtered", "lm_index_search_filtered_device",
     "lm_pq_scan", "lm_pq_scan_workspace_bytes", "lm_pq_flat_search", "lm_pq_flat_search_device",
@@ -179,6 +179,7 @@ def load() -> C.CDLL:
     lib.lm_graph_prune_hubs_workspace_bytes.argtypes = [i64, i32, i32, i64]
     lib.lm_graph_prune_hubs_workspace_bytes.restype = C.c_size_t
     lib.lm_graph_prune_hubs.argtypes = [vp, i32, i32, i32, vp, i64, i32, i32, i64, C.c_float, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.lm_graph_insert_batch.argtypes = [vp, vp, i64, i32, i32, i32, C.c_float, C.POINTER(SearchParams), vp, vp, vp, vp, vp, vp]
     lib.lm_pq_encode.argtypes = [vp, i32, i64, i32, i32, i32, vp, vp, vp, vp]
     lib.lm_pq_train.argtypes = [vp, i32, i64, i32, i32, i32, vp, i32, vp, vp, C.c_size_t, vp]
     lib.lm_pq_train_workspace_bytes.argtypes = [i64, i32, i32]

@@ -142,7 +142,10 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         (bool, default False): both of these insert their links with the library's kernel (lm_graph_add_links) instead of torch ops.
         ``gpu_search_view`` (bool, default False): the GPU builder searches its level graphs in place through a view index
         (lm_index_create_view, build_graph_gpu(search="view")) instead of re-assembling a CSR for every insert batch; needs
-        ``gpu_link_kernel``.  ``gpu_prune_kernel`` (bool, default False): the pruning runs as one library call on the device
+        ``gpu_link_kernel``.  ``gpu_insert_kernel`` (bool, default False): every insert batch and refinement step of the GPU builder is one
+        library call on the level's view (lm_graph_insert_batch, build_graph_gpu(inserter="kernel")) instead of torch ops between the
+        kernels; needs ``gpu_select_kernel``, ``gpu_link_kernel`` and ``gpu_search_view``, and builds the same graph byte for byte.
+        ``gpu_prune_kernel`` (bool, default False): the pruning runs as one library call on the device
         (lm_graph_prune_hubs, prune_preserving_hubs(pruner="kernel")): in-degrees, hub choice -- ties at the cut go to the lower id --,
         link weights and the link insertion, instead of numpy / torch ops on the host's copy of the graph."""
         from .hnsw_builder import build_hnsw
@@ -154,6 +157,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         linker = "kernel" if bool(bp.get("gpu_link_kernel", False)) else "torch"
         search = "view" if bool(bp.get("gpu_search_view", False)) else "csr"
         prune_kernel = bool(bp.get("gpu_prune_kernel", False))
+        insert_kernel = bool(bp.get("gpu_insert_kernel", False))
         use_gpu = data.shape[0] >= thr and _lib.device_count() > 0
         if not use_gpu and m_low <= 0:
             return build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
@@ -163,7 +167,8 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
 
         if use_gpu:
             x = torch.from_numpy(np.ascontiguousarray(data)).to(torch.device("cuda", int(bp.get("device", 0))))
-            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker, search=search)
+            g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker, search=search,
+                                **({"inserter": "kernel"} if insert_kernel else {}))  # (absent: build_graph_gpu's default, the torch ops)
         else:
             x = torch.from_numpy(np.ascontiguousarray(data))
             if selector == "kernel" or linker == "kernel" or (prune_kernel and m_low > 0):  # the pruning below then runs the kernel: it reads the embeddings from HBM (no CPU form of it exists)

@@ -17,6 +17,8 @@
 //   lm_link_impl.h    index build time: link insertion (lm_graph_add_links): k_link_count / k_link_scan / k_link_fill / k_link_row
 //   lm_prune_impl.h   index build time: hub-preserving pruning (lm_graph_prune_hubs): k_prune_indeg / k_prune_hist / k_prune_pick / k_prune_scan /
 //                     k_prune_emit / k_prune_sort_*, then lm_link_impl.h's launch sequence
+//   lm_insert_impl.h  index build time: one builder insert step on a view index (lm_graph_insert_batch): k_insert_queries, the view search,
+//                     k_insert_merge, lm_select_impl.h's launch, k_insert_edges, then lm_link_impl.h's launch sequence
 //   lm_view_impl.h    lm_index_create_view: k_search_table's dense-level graph accessor (fixed-capacity level adjacencies searched in place)
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
@@ -111,6 +113,12 @@ struct lm_index {
     // workspaces in bytes, apart from the graph search's: lm_index_search_exact*'s partial top-k lists, lm_pq_flat_search*'s partial lists,
     // lm_index_search_filtered*'s per-pass result lists and per-query counts
     DevBuf<unsigned char> d_exact_ws, d_pqflat_ws, d_filter_ws;
+    // lm_graph_insert_batch (lm_insert_impl.h): the batch's queries, its search result, candidates, keep mask, edges and the link insertion's workspace
+    DevBuf<float> d_ins_q, d_ins_sd, d_ins_cdist, d_ins_w;
+    DevBuf<int64_t> d_ins_sl;
+    DevBuf<int32_t> d_ins_cand, d_ins_src, d_ins_dst;
+    DevBuf<uint8_t> d_ins_keep;
+    DevBuf<unsigned char> d_ins_ws;
     int64_t filtered_allowed_evals = 0;  // option "filtered_allowed_evals" (read only): (query, node) pairs of the last filtered call that passed the allow test
     std::vector<int32_t> h_pq_chunk_off;  // host copy of d_pq_chunk_off (m + 1)
     unsigned long long* h_counters = nullptr;  // pinned
@@ -1258,4 +1266,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_pq_flat_impl.h"
 #include "lm_link_impl.h"
 #include "lm_prune_impl.h"
+#include "lm_insert_impl.h"
 

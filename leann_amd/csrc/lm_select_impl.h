@@ -68,12 +68,8 @@ __global__ __launch_bounds__(256) void k_select_neighbors(const void* table, int
     }
 }
 
-}  // namespace lm
-
-extern "C" {
-
-int lm_select_neighbors(const void* d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric, const int32_t* d_cand,
-                        const float* d_dist, int64_t n, int32_t K, int32_t m, float alpha, uint8_t* d_keep, void* stream) {
+// what lm_select_neighbors rejects before it looks at a buffer
+inline int select_check_params(int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric, int64_t n, int32_t K, int32_t m, float alpha) {
     if (d_padded <= 0 || d_padded % 64) LM_FAIL(LM_EINVAL, "d_padded must be a positive multiple of 64");
     if (K < 1 || K > LM_SELECT_MAX_K) LM_FAIL(LM_EINVAL, "K must be in [1, LM_SELECT_MAX_K = " + std::to_string(LM_SELECT_MAX_K) + "]");
     if (m < 1) LM_FAIL(LM_EINVAL, "m must be >= 1");
@@ -86,12 +82,15 @@ int lm_select_neighbors(const void* d_table, int32_t dtype, int64_t ntable, int3
         default: LM_FAIL(LM_EINVAL, "unsupported padded dimension (supported: 64..384, 512, 768, 1024)");
     }
     if ((n + 15) / 16 > 0x7fffffffll) LM_FAIL(LM_EINVAL, "n too large for one launch");
-    if (n == 0) return LM_OK;
-    if (!d_cand || !d_dist || !d_keep || (ntable > 0 && !d_table)) LM_FAIL(LM_EINVAL, "NULL buffer");
+    return LM_OK;
+}
+
+// the launch of lm_select_neighbors on checked arguments (n >= 1): both it and lm_graph_insert_batch (lm_insert_impl.h) enqueue exactly this
+inline int select_launch(const void* d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric, const int32_t* d_cand, const float* d_dist, int64_t n,
+                         int32_t K, int32_t m, float alpha, uint8_t* d_keep, hipStream_t st) {
     const float a2 = alpha * alpha;
     const int relaxed = alpha != 1.0f ? 1 : 0;
     dim3 grid((unsigned)((n + 15) / 16)), block(256);
-    hipStream_t st = (hipStream_t)stream;
     const bool l2 = metric == LM_METRIC_L2, f16 = dtype == LM_DTYPE_F16;
 #define GO(nch)                                                                                                                                  \
     case nch:                                                                                                                                    \
@@ -106,6 +105,19 @@ int lm_select_neighbors(const void* d_table, int32_t dtype, int64_t ntable, int3
 #undef GO
     LM_HIP(hipGetLastError());
     return LM_OK;
+}
+
+}  // namespace lm
+
+extern "C" {
+
+int lm_select_neighbors(const void* d_table, int32_t dtype, int64_t ntable, int32_t d_padded, int32_t metric, const int32_t* d_cand,
+                        const float* d_dist, int64_t n, int32_t K, int32_t m, float alpha, uint8_t* d_keep, void* stream) {
+    using namespace lm;
+    if (int rc = select_check_params(dtype, ntable, d_padded, metric, n, K, m, alpha)) return rc;
+    if (n == 0) return LM_OK;
+    if (!d_cand || !d_dist || !d_keep || (ntable > 0 && !d_table)) LM_FAIL(LM_EINVAL, "NULL buffer");
+    return select_launch(d_table, dtype, ntable, d_padded, metric, d_cand, d_dist, n, K, m, alpha, d_keep, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -396,6 +396,7 @@ def _assemble_csr(levels_top: np.ndarray, graphs: "list[tuple[np.ndarray, np.nda
 
 
 SEARCHES = ("csr", "view")
+INSERTERS = ("torch", "kernel")
 
 
 class _LevelView:
@@ -443,6 +444,12 @@ class _LevelView:
                                                        C.byref(prm)), "lm_index_search_device")
         return ids, (dist if self.metric == METRIC_INNER_PRODUCT else -dist)
 
+    def insert(self, G: "_LevelGraph", batch: torch.Tensor, replace: bool, ef: int, kk: int, m: int, alpha: float):
+        """One insert step as ONE library call (lm_graph_insert_batch: search, candidates, selection, both link directions) on ``G``'s own
+        arrays -- build_graph_gpu(inserter="kernel").  Same search parameters as :meth:`search`."""
+        prm = self.idx.make_params(ef=ef, beam=self.beam, recompute=False, max_batch=16384)
+        self.idx.insert_batch(batch.to(torch.int32).contiguous(), replace, kk, m, alpha, prm, G.adj, G.dist, G.deg)
+
     def close(self):
         self.idx.close()
 
@@ -487,7 +494,7 @@ def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
 def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_construction: int = 200, seed: int = 12345,
                     search_fn: Optional[SearchFn] = None, growth: float = 1.5, k_cand: int = 0,
                     seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch",
-                    linker: str = "torch", search: str = "csr") -> HnswCsr:
+                    linker: str = "torch", search: str = "csr", inserter: str = "torch") -> HnswCsr:
     """x: [N, D] float tensor on the build device.  Returns the compact-CSR HNSW graph (host).  ``alpha`` > 1 relaxes the neighbour
     selection the way Vamana does (denser lists with longer edges: what a PQ-guided walk over a flat graph needs at 10M nodes -- DESIGN 8;
     inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on.
@@ -499,13 +506,21 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
     ``search``: "csr" (default) = every insert batch assembles the graph built so far as a CSR on the host, uploads it as a fresh index
     and searches that (``search_fn``; by default hip_search_fn); "view" = one view index per level (lm_index_create_view) searches the
     level adjacencies where lm_graph_add_links keeps them -- it needs linker="kernel" (the int32 adjacency updated in place) and takes no
-    ``search_fn``.  With selector="kernel" and linker="kernel" both build the same graph byte for byte."""
+    ``search_fn``.  With selector="kernel" and linker="kernel" both build the same graph byte for byte.
+    ``inserter``: "torch" (default) = the step between the kernels (candidate merge and dedupe in refinement, keep mask -> edge lists,
+    row clearing) by torch ops, with a host synchronisation per boolean-mask indexing and one ``inserted.sum()`` per batch; "kernel" =
+    every insert batch and every refinement step is ONE lm_graph_insert_batch call on the level's view, and the number of inserted
+    nodes is counted on the host.  It needs selector="kernel", linker="kernel" and search="view", and builds the same graph byte for byte."""
     select = _selector_fn(selector)
     _check_linker(linker)
     if search not in SEARCHES:
         raise ValueError(f"search must be one of {SEARCHES}, not {search!r}")
     if search == "view" and linker != "kernel":
         raise ValueError('search="view" needs linker="kernel": the view reads the int32 adjacency that lm_graph_add_links updates in place')
+    if inserter not in INSERTERS:
+        raise ValueError(f"inserter must be one of {INSERTERS}, not {inserter!r}")
+    if inserter == "kernel" and not (selector == "kernel" and linker == "kernel" and search == "view"):
+        raise ValueError('inserter="kernel" needs selector="kernel", linker="kernel" and search="view": lm_graph_insert_batch is those three on one view index')
     if search == "view" and search_fn is not None:
         raise ValueError('search="view" searches through its own view index: it takes no search_fn')
     metric = metric.lower()
@@ -551,6 +566,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             s[:, : up.cap][m] = up_sim[m]
             G.seed_rows(loc, a, s)
             inserted[loc] = True
+            n_inserted = int(loc.shape[0])  # (the seed set's size is a shape: known without asking the device)
         else:
             ns = min(nl, seed_nodes)
             perm0 = torch.randperm(nl, generator=gen)[:ns].to(dev)
@@ -564,6 +580,7 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
                 w = cs[keep]
                 G.add_links(xlink, torch.cat([src, dst]), torch.cat([dst, src]), torch.cat([w, w]), mt)
             inserted[perm0] = True
+            n_inserted = int(perm0.shape[0])
         rest = torch.nonzero(~inserted).flatten()
         rest = rest[torch.randperm(rest.shape[0], generator=gen).to(dev)]
         # levels (relative to l) of the nodes of this subset, for the temporary search structure
@@ -575,6 +592,12 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             return _assemble_csr(rel_top, graphs, sub_np, d, mt, entry_global, M, ef_construction)
 
         view: "list[_LevelView]" = []  # search="view": this level's view index, created at the first insert batch
+
+        def insert_kernel(batch: torch.Tensor, replace: bool, have: int):
+            kk = min(k_cand + (1 if replace else 0), max(have - 1, 1))
+            if not view:
+                view.append(_LevelView(G, finished, xs, xlink if xlink.dtype == torch.float32 else _padded_table(xs.float()), mt, entry_global))
+            view[0].insert(G, batch, replace, max(ef_construction, kk), kk, M, alpha)
 
         def insert(batch: torch.Tensor, replace: bool):
             kk = min(k_cand + (1 if replace else 0), max(int(inserted.sum()) - 1, 1))
@@ -616,6 +639,14 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             inserted[batch] = True
 
         pos = 0
+        while inserter == "kernel" and pos < rest.shape[0]:  # the loop below with the count kept on the host: the seed set plus the batches so far
+            bs = max(256, int(n_inserted * (growth - 1.0)))
+            batch = rest[pos : pos + bs]
+            insert_kernel(batch, False, n_inserted)
+            pos += batch.shape[0]
+            n_inserted += int(batch.shape[0])
+            if verbose:
+                print(f"[build] level {l}: {n_inserted}/{nl} nodes, mean degree {float(G.deg.sum()) / n_inserted:.1f}")
         while pos < rest.shape[0]:
             have = int(inserted.sum())
             bs = max(256, int(have * (growth - 1.0)))
@@ -628,7 +659,10 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
             allb = torch.arange(nl, device=dev)
             step = max(4096, nl // 8)
             for b0 in range(0, nl, step):
-                insert(allb[b0 : b0 + step], replace=True)
+                if inserter == "kernel":
+                    insert_kernel(allb[b0 : b0 + step], True, nl)  # (every node of the level is in by now)
+                else:
+                    insert(allb[b0 : b0 + step], replace=True)
             if verbose:
                 print(f"[build] level {l}: refined, mean degree {float(G.deg.float().mean()):.1f}")
         if view:

@@ -244,6 +244,33 @@ class Mi355xIndex:
         self._raise_provider(rc, "lm_index_search_device")
         return dist, labels
 
+    # ---- index build time: one insert step of the batched builder on a view -------------------------
+    def insert_batch(self, batch, replace: bool, kk: int, m: int, alpha: float, params: SearchParams, adj, dist, deg, return_candidates: bool = False):
+        """lm_graph_insert_batch on a view (:meth:`from_levels`) with a table attached: search the level as it stands for the nodes ``batch``
+        (an int32 tensor [b]), form their candidates (``replace``: merged with their current rows, which are then cleared), select at most
+        ``m`` neighbours and link both directions, all on the index's stream.  ``adj`` must be the view's level-0 tensor; ``dist`` [n, cap]
+        fp32 and ``deg`` [n] int32 are that level's other two arrays (lm_graph_add_links' layout); all three are updated in place.  The tensors
+        live where the library's kernels run (the host build of the library, which the CPU tests load, takes host tensors).
+        ``return_candidates``: -> (cand int32 [b, K], cdist fp32 [b, K], keep uint8 [b, K]), K = kk (+ cap when ``replace``); else None."""
+        import torch
+
+        b = int(batch.shape[0])
+        if not (batch.dtype == torch.int32 and batch.dim() == 1 and batch.is_contiguous()):
+            raise ValueError("batch must be a contiguous int32 tensor [b]")
+        for t, dt, nm in ((adj, torch.int32, "adj"), (dist, torch.float32, "dist"), (deg, torch.int32, "deg")):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{nm} must be a contiguous {dt} tensor")
+        outs = (None, None, None)
+        if return_candidates:
+            K = int(kk) + (adj.shape[1] if replace else 0)
+            outs = (torch.empty((b, K), dtype=torch.int32, device=adj.device), torch.empty((b, K), dtype=torch.float32, device=adj.device),
+                    torch.empty((b, K), dtype=torch.uint8, device=adj.device))
+        ptr = [None if (t is None or t.numel() == 0) else C.c_void_p(t.data_ptr()) for t in outs]
+        rc = self._lib.lm_graph_insert_batch(self._h, C.c_void_p(batch.data_ptr()) if b else None, b, 1 if replace else 0, int(kk), int(m), float(alpha), C.byref(params),
+                                             C.c_void_p(adj.data_ptr()) if adj.numel() else None, C.c_void_p(dist.data_ptr()), C.c_void_p(deg.data_ptr()), *ptr)
+        check(rc, "lm_graph_insert_batch")
+        return outs if return_candidates else None
+
     # ---- graph search with an allow-list ----------------------------------------------------------
     def search_filtered(self, queries: np.ndarray, k: int, params: SearchParams, allowed=None):
         """:meth:`search` with an allow-list (lm_index_search_filtered): the same walk, the best k of the ALLOWED nodes it evaluated; (distances,
