@@ -188,7 +188,14 @@ void lm_search_params_default(lm_search_params *p);
  *                                                           hnsw_backend.py:241-248.
  * x: n x d fp32 queries (host).  distances: n x k fp32, labels: n x k int64, caller-allocated
  * (hnsw_backend.py:236-238).  l2: squared L2 ascending; inner product: +IP descending.
- * Unfilled slots: label -1, distance +inf (l2) / -inf (ip). */
+ * Unfilled slots: label -1, distance +inf (l2) / -inf (ip).
+ * LDS rule of a CSR index: with maxnew = max(beam_size * largest level-0 degree, largest upper-level degree, 1) -- and, where
+ * batch_size > 0, at least batch_size - 1 + largest level-0 degree -- and P(x) = the next power of two, a stored-embedding search
+ * that the persistent launch serves (recompute = 0, no pq_pruning_ratio, batch_size = 0, beam_size <= 64, options "persistent_table" 1
+ * and "update_variant" 0) needs (2 * max(efSearch, k) + P(maxnew)) * 8 + 4 * maxnew <= 150 KiB of LDS; every other search, and that
+ * one where it needs more, runs the lock-step rounds, which need (2 * max(efSearch, k) + P(maxnew)) * 8 <= 64 KiB.  What fits neither
+ * is LM_EINVAL (lm_last_error names the LDS), decided in 64-bit arithmetic before the search workspace is allocated or anything is launched: the
+ * outputs are untouched and the handle serves the next call.  That covers any beam_size and batch_size up to INT32_MAX. */
 int lm_index_search(lm_index *idx, int64_t n, const float *x, int32_t k, float *distances,
                     int64_t *labels, const lm_search_params *params);
 /* Same with queries and results resident in HBM (no PCIe in the timed region). */

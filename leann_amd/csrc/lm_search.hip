@@ -162,10 +162,25 @@ static int ws_alloc(lm_index* ix, T** p, size_t count) {
     return LM_OK;
 }
 
-static int ensure_ws(lm_index* ix, int32_t B, int32_t ef, int32_t W, bool prune = false, int32_t spec = 0, int32_t batch = 0) {
-    int32_t maxnew = std::max({W * ix->maxdeg0, ix->maxdeg_up, 1});
+// The longest new-list one round can hand a query, in 64 bits: beam_size and batch_size are the caller's and their products with a degree
+// pass 2^31 (search_lds_checks refuses what does not fit the LDS with these numbers, before anything is allocated).
+static int64_t ws_maxnew(const lm_index* ix, int64_t W, bool prune, int64_t batch) {
+    int64_t maxnew = std::max<int64_t>({W * ix->maxdeg0, (int64_t)ix->maxdeg_up, (int64_t)1});
     if (batch > 0) maxnew = std::max(maxnew, batch - 1 + ix->maxdeg0);  // dynamic batching: the last extra pop starts below `batch` and adds one list at most
-    if (prune) maxnew = std::max(maxnew, (int32_t)AQ_CAP);
+    if (prune) maxnew = std::max(maxnew, (int64_t)AQ_CAP);
+    return maxnew;
+}
+
+static int64_t next_pow2_64(int64_t x) {
+    int64_t p = 1;
+    while (p < x) p <<= 1;
+    return p;
+}
+
+static int ensure_ws(lm_index* ix, int32_t B, int32_t ef, int32_t W, bool prune = false, int32_t spec = 0, int32_t batch = 0) {
+    const int64_t maxnew64 = ws_maxnew(ix, W, prune, batch);
+    if (maxnew64 > (1 << 24)) LM_FAIL(LM_EINVAL, "beam_size / batch_size too large: a round's new-list would not fit the LDS");  // (no kernel's LDS holds that many ids)
+    const int32_t maxnew = (int32_t)maxnew64;
     if (B <= ix->ws_B && ef == ix->ws_ef && W == ix->ws_W && maxnew == ix->ws_maxnew && spec == ix->ws_spec) {
         ix->ws.B = B;
         return LM_OK;
@@ -419,6 +434,8 @@ static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GA& g, s
 
 #define VIEW_LDS_TEXT "efSearch / k / beam_size too large for a view index: (2*max(efSearch,k) + P(maxnew)) * 8 + 4 * maxnew bytes, maxnew = max(beam_size * levels[0].cap, largest upper cap, 1), must fit 150 KiB"
 
+#define LOCKSTEP_LDS_TEXT "efSearch / beam_size / batch_size too large for the LDS-resident pool (2*max(efSearch,k) + max(beam*max_degree, batch_size + max_degree) keys must fit 64 KiB)"
+
 // Everything a search on a view refuses, in front of any staging or launch (NULL / range errors of the arguments are left to do_search_device,
 // which reports them for every index alike).
 static int view_checks(const lm_index* ix, int64_t n, int32_t k, const lm_search_params* prm) {
@@ -569,8 +586,7 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     {
         // dynamic LDS of the update kernel (default launch limit 64 KiB): pool | merged pool | new keys
         const size_t need = ((size_t)2 * ef + next_pow2(ws.maxnew)) * 8;
-        if (need > 64 * 1024)
-            LM_FAIL(LM_EINVAL, "efSearch / beam_size / batch_size too large for the LDS-resident pool (2*max(efSearch,k) + max(beam*max_degree, batch_size + max_degree) keys must fit 64 KiB)");
+        if (need > 64 * 1024) LM_FAIL(LM_EINVAL, LOCKSTEP_LDS_TEXT);  // (do_search_device refuses this before anything is allocated: search_lds_checks)
     }
     const int ntiles = (int)((ws.nw + UNIQ_TILE - 1) / UNIQ_TILE);
     const int sync_every = recompute ? 1 : 4;
@@ -679,6 +695,19 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     return LM_OK;
 }
 
+// The LDS rules of a CSR index, decided in 64 bits in front of the first allocation: whichever kernel the call will run -- the persistent
+// launch (`persistent`: its conditions hold; 150 KiB: pool | merged pool | new keys | new ids) or the lock-step rounds (64 KiB: pool |
+// merged pool | new keys) -- its state must fit, else LM_EINVAL and no workspace is allocated, nothing launched.  search_pass_persistent and
+// search_pass keep their own checks: with this one in front they never fail.  *fits_persistent: the persistent launch will take the call.
+static int search_lds_checks(const lm_index* ix, int32_t k, const lm_search_params& prm, bool persistent, bool* fits_persistent) {
+    const int64_t ef = std::max(prm.efSearch, k), W = std::max(prm.beam_size, 1);
+    const int64_t maxnew = ws_maxnew(ix, W, prm.pq_pruning_ratio > 0.0f, prm.batch_size);
+    const int64_t keys = 2 * ef + next_pow2_64(maxnew);
+    *fits_persistent = persistent && keys * 8 + 4 * maxnew <= 150 * 1024;
+    if (!*fits_persistent && keys * 8 > 64 * 1024) LM_FAIL(LM_EINVAL, LOCKSTEP_LDS_TEXT);
+    return LM_OK;
+}
+
 // flt != NULL: lm_index_search_filtered* (the lock-step rounds with k_filter_collect); NULL: the launches are exactly those of the unfiltered search
 static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k, float* d_dist, int64_t* d_labels,
                             const lm_search_params* params, const FilterPass* flt = nullptr) {
@@ -708,22 +737,26 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     } else if (!ix->d_table) {
         LM_FAIL(LM_ESTATE, "index stores no embeddings (pruned): recompute is required");
     }
+    // the persistent launch's condition (search_pass_persistent declines when its LDS does not fit: search_lds_checks makes that decision here)
+    const bool persistent = ix->view || (!prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table &&
+                                         ix->update_variant == 0 && std::max(prm.beam_size, 1) <= 64);  // (a view: view_checks has established the rest)
+    bool fits_persistent = ix->view;
+    if (!ix->view)  // a filtered search runs the lock-step rounds whatever `persistent` says
+        if (int lrc = search_lds_checks(ix, k, prm, persistent && !flt, &fits_persistent)) return lrc;
     const float* d_q = nullptr;
     if (int prc = pad_queries(ix, n, d_x, &d_q)) return prc;
     int64_t maxb = prm.max_batch > 0 ? prm.max_batch : 4096;
     // bound the visited bitmaps to 8 GiB
     int64_t nwbytes = ((ix->N + 31) / 32) * 4;
     maxb = std::max<int64_t>(1, std::min<int64_t>(maxb, (8ll << 30) / std::max<int64_t>(nwbytes, 1)));
-    // the persistent launch's condition (search_pass_persistent declines when its LDS does not fit: its own check, restated for the filtered search)
-    const bool persistent = ix->view || (!prm.recompute && prm.pq_pruning_ratio <= 0.0f && prm.batch_size == 0 && ix->persistent_table &&
-                                         ix->update_variant == 0 && std::max(prm.beam_size, 1) <= 64);  // (a view: view_checks has established the rest)
     FilterPass fpass{};
     if (flt) {
         // The stats of a filtered call are those of lm_index_search on the same inputs.  Where that call runs the persistent launch, its nrounds
         // is the longest pass's, not the sum over the passes: report the same.
-        const int32_t maxnew = std::max({std::max(prm.beam_size, 1) * ix->maxdeg0, ix->maxdeg_up, 1});
+        bool unfiltered_persistent = false;
+        if (int lrc = search_lds_checks(ix, k, prm, persistent, &unfiltered_persistent)) return lrc;  // (cannot fail: the lock-step rule held above)
         fpass = *flt;
-        fpass.rounds_max = persistent && ((size_t)2 * std::max(prm.efSearch, k) + next_pow2(maxnew)) * 8 + (size_t)maxnew * 4 <= 150 * 1024;
+        fpass.rounds_max = unfiltered_persistent;
         flt = &fpass;
     }
     for (int64_t off = 0; off < n; off += maxb) {
@@ -731,7 +764,7 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
         int rc = 1;
         // (dynamic batching exists to fill the recompute forward: a stored-embedding search that asks for it runs the lock-step kernels, which implement it)
         // (a filtered search collects its result round by round: lock-step too)
-        if (!flt && persistent)
+        if (!flt && fits_persistent)
             rc = search_pass_persistent(ix, B, d_q + (size_t)off * ix->Dp, k, prm, d_dist + (size_t)off * k, d_labels + (size_t)off * k);
         if (rc == 1 && ix->view) LM_FAIL(LM_ESTATE, "internal: a view index has no lock-step search");
         if (rc == 1)  // not applicable (or LDS budget exceeded): lock-step rounds
