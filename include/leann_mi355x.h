@@ -849,7 +849,22 @@ int64_t lm_tokens_count(const lm_tokens *t);
  *                                    compute the round's chunk lengths before its own per-round device-to-host copy: ONE host
  *                                    synchronisation per round (lm_index_set_provider with a foreign callback: the callback's own);
  *   lm_recompute_provider            the same object as a plain lm_provider_fn (user = the handle), e.g. for lm_index_set_provider;
- *   lm_recompute_embed               embeddings of n chunk ids into the caller's fp32 [n][hidden] buffer (index build time). */
+ *   lm_recompute_embed               embeddings of n chunk ids into the caller's fp32 [n][hidden] buffer (index build time).
+ *
+ * Lanes (lm_recompute_set_option / lm_recompute_get_option; added without a new ABI revision: no existing entry point, struct or enum
+ * changed).  A forward is a chain of ~20 dependent launches, and each launch drains the chip before the next starts.  With "lanes" 2 or 3 the
+ * handle owns 1 or 2 non-blocking streams next to the caller's and a call's forwards run on them concurrently: a call within the token
+ * budget is split into that many contiguous chunk ranges of about equal token count -- only if every part holds more than
+ * "lane_min_tokens" tokens (>= 256; default LM_RC_LANE_MIN_TOKENS, no smaller than the large-forward thresholds above) --, a call
+ * above the budget deals its forwards round-robin to the lanes.  Every part runs the kernels chosen for the whole, and a chunk's
+ * embedding does not depend on its neighbours in a forward, so the embeddings are the same bits at every lane count.  The lanes start
+ * behind everything queued on the caller's stream before the call, and the caller's stream waits for all of them before the call
+ * returns: what the caller queues next is ordered as with one lane.  "lanes" 1 is the single-stream provider.  The environment variable
+ * LEANN_MI355X_FORWARD_LANES (1..3), read once at create, overrides the default LM_RC_DEFAULT_LANES (A/B).  Set options between calls,
+ * from the thread that makes them.  lm_recompute_stats.forwards counts a forward once however many parts it ran as;
+ * lm_recompute_get_option "parts" (read-only) counts the parts. */
+#define LM_RC_LANE_MIN_TOKENS LM_BERT_QKV_GEMM_TOKENS
+#define LM_RC_DEFAULT_LANES 3
 typedef struct lm_recompute lm_recompute;
 typedef struct lm_recompute_stats {
     int64_t calls, chunks, tokens, forwards, host_syncs;
@@ -862,6 +877,8 @@ void lm_recompute_free(lm_recompute *rc);
 int lm_recompute_provider(void *user, const int32_t *d_ids, int32_t n, void **d_out, void *stream);
 int lm_recompute_embed(lm_recompute *rc, const int32_t *d_ids, int32_t n, float *d_out, void *stream);
 int lm_recompute_get_stats(const lm_recompute *rc, lm_recompute_stats *out);
+int lm_recompute_set_option(lm_recompute *rc, const char *name, int64_t value);
+int lm_recompute_get_option(const lm_recompute *rc, const char *name, int64_t *out);
 int lm_index_set_recompute(lm_index *idx, lm_recompute *rc);
 
 /* ---- measurement: event pairs around the library's own launches of the encoder's MFMA kernels (csrc/lm_timing.cpp) ----

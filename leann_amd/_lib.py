@@ -126,7 +126,7 @@ EXPORTED_SYMBOLS = [
     "lm_tokens_create", "lm_tokens_free", "lm_tokens_gather", "lm_tokens_count",
     "lm_bert_h384_workspace_bytes", "lm_bert_h384_forward_packed",
     "lm_bert_workspace_bytes", "lm_bert_forward_packed", "lm_clspool_varlen_f16",
-    "lm_recompute_create", "lm_recompute_create_general", "lm_recompute_free", "lm_recompute_provider", "lm_recompute_embed", "lm_recompute_get_stats", "lm_index_set_recompute",
+    "lm_recompute_create", "lm_recompute_create_general", "lm_recompute_free", "lm_recompute_provider", "lm_recompute_embed", "lm_recompute_get_stats", "lm_recompute_set_option", "lm_recompute_get_option", "lm_index_set_recompute",
     "lm_kernel_timing_enable", "lm_kernel_timing_read",
 ]
 
@@ -238,6 +238,8 @@ def load() -> C.CDLL:
     lib.lm_recompute_provider.argtypes = [vp, vp, i32, C.POINTER(vp), vp]
     lib.lm_recompute_embed.argtypes = [vp, vp, i32, vp, vp]
     lib.lm_recompute_get_stats.argtypes = [vp, C.POINTER(RecomputeStats)]
+    lib.lm_recompute_set_option.argtypes = [vp, C.c_char_p, i64]
+    lib.lm_recompute_get_option.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
     lib.lm_index_set_recompute.argtypes = [vp, vp]
     lib.lm_kernel_timing_enable.argtypes = [C.c_uint32]
     lib.lm_kernel_timing_read.argtypes = [C.POINTER(KernelTime), i32, i32]

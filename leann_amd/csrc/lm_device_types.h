@@ -57,8 +57,9 @@ struct WsDev {
     unsigned long long* counters;
 };
 // C_RC_TOKENS / C_RC_MAXLEN: total tokens and longest chunk of the round's unique list, written by the built-in recompute provider's
-// length scan (lm_recompute.hip) so that the loop's one device-to-host copy per round carries them
-enum { C_LIVE = 0, C_NUNIQ = 1, C_NDIS = 2, C_NEXPAND = 3, C_ROUNDS = 4, C_RC_TOKENS = 5, C_NADC = 6, C_RC_MAXLEN = 7, C_PQ_OVERFLOW = 8, C_PQ_ALLOWED = 9, C_NCOUNTERS = 10 };
+// length scan (lm_recompute.hip) so that the loop's one device-to-host copy per round carries them.  C_RC_SPLIT, C_RC_SPLIT + 1: that
+// scan's split points for a forward run as concurrent lanes (lm_rc_parts.h: rc_split_pack), written only while the provider has lanes
+enum { C_LIVE = 0, C_NUNIQ = 1, C_NDIS = 2, C_NEXPAND = 3, C_ROUNDS = 4, C_RC_TOKENS = 5, C_NADC = 6, C_RC_MAXLEN = 7, C_PQ_OVERFLOW = 8, C_PQ_ALLOWED = 9, C_RC_SPLIT = 10, C_NCOUNTERS = 12 };
 
 constexpr int UNIQ_TILE = 4096;  // words per block in the uniq scan
 constexpr int AQ_CAP = 512;       // capacity of the approximate queue (== ORC_AQ_CAP in oracle/lm_oracle.c)

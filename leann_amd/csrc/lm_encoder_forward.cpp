@@ -58,10 +58,33 @@ extern "C" size_t lm_bert_h384_workspace_bytes(int64_t total_tokens) {
     return (size_t)total_tokens * (3 * 384 + 1152) * 2 + small;
 }
 
+// The three choices of a hidden-384 forward that depend on its SIZE -- taken once, from the totals of the forward as its caller decided it.
+// The recompute provider runs one such forward as several concurrent parts (lm_recompute.hip: lanes): every part gets the plan of the
+// whole, so a part never lands on other kernels than the unsplit forward would (their fp16 results differ in the last bits).
+lm::BertH384Plan lm::bert_h384_plan(const lm_bert_h384* m, int32_t n_seqs, int64_t total_tokens, int32_t max_len) {
+    BertH384Plan p;
+    p.small = total_tokens <= small_tokens_limit() && m->ffn % 128 == 0;  // (every multiple of 192 in the envelope that is one of 128: 384, 768, 1152, 1536, ...)
+    for (int l = 0; p.small && l < m->n_layers; ++l) p.small = m->layers[l].wo && m->layers[l].w1 && m->layers[l].w2;
+    p.first_half = h384_first_half_form(m->heads, max_len, total_tokens, n_seqs);  // one decision per forward, shared with the Python host's launch path
+    p.qkv_gemm = !p.small && total_tokens <= qkv_gemm_tokens_limit();  // a forward that fills a fraction of the chip: QKV from the general GEMM
+    for (int l = 0; p.qkv_gemm && l < m->n_layers; ++l) p.qkv_gemm = m->layers[l].wqkv != nullptr;
+    const char* f = getenv("LEANN_MI355X_FUSED_QKV_ATTN");
+    if (p.qkv_gemm && f && f[0] == '1') p.qkv_gemm = false;  // (the fused kernel forced: it has no stand-alone projection)
+    else if (p.qkv_gemm) p.first_half = H384_PAIR_ROW_MAJOR;
+    return p;
+}
+
 extern "C" int lm_bert_h384_forward_packed(const lm_bert_h384* m, const int32_t* d_tok, const int32_t* d_pos, const int32_t* d_cu_seqlens,
                                            int32_t n_seqs, int64_t total_tokens, int32_t max_len, void* d_workspace, size_t workspace_bytes,
                                            float* d_out, void* stream) {
-    using namespace lm;
+    return lm::bert_h384_forward_planned(m, d_tok, d_pos, d_cu_seqlens, n_seqs, total_tokens, max_len, d_workspace, workspace_bytes, d_out, nullptr, stream);
+}
+
+// plan == nullptr: this forward is the whole (the C ABI's entry); max_len sizes attention's key-tile template only (LDS and the staging
+// loop: lm_attn_v3.hip / lm_attn_v2.hip walk each sequence by ITS length), so a part may pass the whole's longest length
+int lm::bert_h384_forward_planned(const lm_bert_h384* m, const int32_t* d_tok, const int32_t* d_pos, const int32_t* d_cu_seqlens, int32_t n_seqs,
+                                  int64_t total_tokens, int32_t max_len, void* d_workspace, size_t workspace_bytes, float* d_out,
+                                  const BertH384Plan* plan, void* stream) {
     if (n_seqs == 0 || total_tokens == 0) return LM_OK;
     if (!m || !m->layers || !d_tok || !d_pos || !d_cu_seqlens || !d_workspace || !d_out || n_seqs < 0 || total_tokens < 0)
         LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: bad arguments");
@@ -77,17 +100,12 @@ extern "C" int lm_bert_h384_forward_packed(const lm_bert_h384* m, const int32_t*
     void* qkv = ws + 3 * row;
     int rc = lm_embed_layernorm_f16(d_tok, d_pos, m->word, m->pos_table, m->type0, m->emb_gamma, m->emb_beta, x, total_tokens, 384, m->ln_eps, stream);
     if (rc) return rc;
-    bool small = total_tokens <= small_tokens_limit() && m->ffn % 128 == 0;  // (every multiple of 192 in the envelope that is one of 128: 384, 768, 1152, 1536, ...)
-    for (int l = 0; small && l < m->n_layers; ++l) small = m->layers[l].wo && m->layers[l].w1 && m->layers[l].w2;
+    const BertH384Plan pl = plan ? *plan : bert_h384_plan(m, n_seqs, total_tokens, max_len);
+    if (pl.small && total_tokens > std::max<int64_t>(small_tokens_limit(), LM_BERT_SMALL_TOKENS))  // (the workspace has [T][ffn] only up to there)
+        LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: a small-forward plan for a forward above the small-forward limit");
+    const bool small = pl.small, qkv_gemm = pl.qkv_gemm;
+    const H384FirstHalf first_half = pl.first_half;
     void* hid = ws + 3 * row + (size_t)total_tokens * 1152 * 2;  // [T][ffn], small forwards only (lm_bert_h384_workspace_bytes)
-    H384FirstHalf first_half = h384_first_half_form(m->heads, max_len, total_tokens, n_seqs);  // one decision per forward, shared with the Python host's launch path
-    bool qkv_gemm = !small && total_tokens <= qkv_gemm_tokens_limit();  // a forward that fills a fraction of the chip: QKV from the general GEMM
-    for (int l = 0; qkv_gemm && l < m->n_layers; ++l) qkv_gemm = m->layers[l].wqkv != nullptr;
-    {
-        const char* f = getenv("LEANN_MI355X_FUSED_QKV_ATTN");
-        if (qkv_gemm && f && f[0] == '1') qkv_gemm = false;  // (the fused kernel forced: it has no stand-alone projection)
-        else if (qkv_gemm) first_half = H384_PAIR_ROW_MAJOR;
-    }
     for (int l = 0; l < m->n_layers; ++l) {
         const lm_bert_h384_layer& L = m->layers[l];
         if (small) {  // every product a grid of small tiles; x -> y (scratch) -> x

@@ -136,9 +136,10 @@ struct lm_tokens {
 // lm_recompute.hip: the search loop's half of the built-in provider's one-synchronisation round
 struct lm_recompute;
 namespace lm {
+// (d_split / split: the two split-point words of a round run as concurrent lanes, lm_rc_parts.h; written only while the handle has lanes)
 int rc_prepare(lm_recompute* rc, const int32_t* d_ids, const unsigned long long* d_n, int64_t cap, unsigned long long* d_total,
-               unsigned long long* d_maxlen, hipStream_t st);
-void rc_prepared(lm_recompute* rc, const int32_t* d_ids, int32_t n, int64_t total, int32_t max_len);
+               unsigned long long* d_maxlen, unsigned long long* d_split, hipStream_t st);
+void rc_prepared(lm_recompute* rc, const int32_t* d_ids, int32_t n, int64_t total, int32_t max_len, const unsigned long long* split);
 int32_t rc_width(const lm_recompute* rc);  // floats per embedding row
 // The ONE envelope of the hidden-384 one-call forward (lm_bert_h384_forward_packed, lm_layer_tail_h384_f16) -- shared with
 // lm_recompute_create, so that a handle it accepts cannot fail on every search round (round-4 advisor finding).
@@ -148,6 +149,17 @@ inline bool bert_h384_envelope_ok(int n_layers, int heads, int ffn) { return n_l
 enum H384FirstHalf : int { H384_FUSED = 0, H384_PAIR_HEAD_MAJOR = 1, H384_PAIR_ROW_MAJOR = 2 };
 constexpr int H384_FUSED_MIN_MEAN_LEN = 216;  // mean sequence length from which the fused kernel is the default (see lm_encoder_forward.cpp)
 H384FirstHalf h384_first_half_form(int32_t heads, int32_t max_len, int64_t total_tokens, int32_t n_seqs);
+// lm_encoder_forward.cpp: what a hidden-384 forward decides from its size, and the forward with that decision handed in (nullptr: taken
+// from this forward's own totals = lm_bert_h384_forward_packed)
+struct BertH384Plan {
+    bool small = false;     // every layer on the general kernels
+    bool qkv_gemm = false;  // large form, QKV projection from the general GEMM
+    H384FirstHalf first_half = H384_PAIR_HEAD_MAJOR;
+};
+BertH384Plan bert_h384_plan(const lm_bert_h384* m, int32_t n_seqs, int64_t total_tokens, int32_t max_len);
+int bert_h384_forward_planned(const lm_bert_h384* m, const int32_t* d_tok, const int32_t* d_pos, const int32_t* d_cu_seqlens, int32_t n_seqs,
+                              int64_t total_tokens, int32_t max_len, void* d_workspace, size_t workspace_bytes, float* d_out, const BertH384Plan* plan,
+                              void* stream);
 
 }  // namespace lm
 

@@ -616,7 +616,7 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
         // needs no second synchronisation inside the provider
         const bool native = recompute && ix->native_rc && ix->provider == lm_recompute_provider && ix->provider_user == (void*)ix->native_rc;
         if (native && (rc = rc_prepare(ix->native_rc, round_ids, ws.counters + C_NUNIQ, single ? (int64_t)ws.maxnew : ix->ws_ucap, ws.counters + C_RC_TOKENS,
-                                       ws.counters + C_RC_MAXLEN, st)) != LM_OK)
+                                       ws.counters + C_RC_MAXLEN, ws.counters + C_RC_SPLIT, st)) != LM_OK)
             return rc;
         bool do_sync = (rounds % sync_every) == 0;
         if (do_sync) {
@@ -628,7 +628,7 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
             int32_t nu = (int32_t)hc[C_NUNIQ];
             void* d_e = nullptr;
             ix->stats.nunique += nu;
-            if (native) rc_prepared(ix->native_rc, round_ids, nu, (int64_t)hc[C_RC_TOKENS], (int32_t)hc[C_RC_MAXLEN]);
+            if (native) rc_prepared(ix->native_rc, round_ids, nu, (int64_t)hc[C_RC_TOKENS], (int32_t)hc[C_RC_MAXLEN], hc + C_RC_SPLIT);
             if (nu > 0) {
                 EvScope es(ix, &ix->ev_provider);
                 int prc = ix->provider(ix->provider_user, round_ids, nu, &d_e, (void*)st);

@@ -25,7 +25,6 @@ struct Pair {
     hipEvent_t a, b;
     int kid, dev;
     double work;
-    void* stream;
 };
 struct Acc {
     int64_t launches = 0;
@@ -33,12 +32,13 @@ struct Acc {
 };
 struct DevState {
     std::vector<hipEvent_t> free_events;
-    // the END event of the last folded pair and its stream: a pair's START event may be stamped while the previous instrumented kernel
-    // of the same stream is still running (nothing orders the record behind it), so back-to-back launches of short kernels would be
-    // counted twice where they overlap -- round 4's C5 line summed 120.7 s of pairs inside a 115.8 s region.  A pair is therefore
-    // charged from max(its start, the previous pair's end).
+    // the LATEST end event among the pairs folded so far, whatever their streams: a pair's START event may be stamped while the previous
+    // instrumented kernel of the same stream is still running (nothing orders the record behind it), so back-to-back launches of short
+    // kernels would be counted twice where they overlap -- round 4's C5 line summed 120.7 s of pairs inside a 115.8 s region -- and the
+    // recompute provider's lanes (lm_recompute.hip) run two launches of the same kernel side by side on two streams ON PURPOSE.  A pair is
+    // therefore charged from max(its start, the latest end seen on its device): time in which several instrumented kernels ran is counted
+    // once, the summed milliseconds never exceed the wall time they lie in; launches and work add up as before.
     hipEvent_t last_end = nullptr;
-    void* last_stream = nullptr;
     unsigned long long* d_attn_work = nullptr;  // [2]: sum over launches of H * sum(len^2) (x 4 = flops), added by k_kt_attn_work -- [0] the stand-alone
                                                 // attention kernels (LM_KT_ATTN), [1] the fused QKV + attention kernel (LM_KT_QKV_ATTN)
 };
@@ -70,9 +70,12 @@ hipEvent_t get_event(int dev) {
 void fold(const Pair& p) {
     DevState& ds = g_dev[p.dev];
     float ms = 0.f;
+    hipEvent_t latest = ds.last_end ? ds.last_end : p.b;
     if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-        float over = 0.f;  // part of [a, b] that lies before the previous pair's end
-        if (ds.last_end && ds.last_stream == p.stream && hipEventElapsedTime(&over, p.a, ds.last_end) == hipSuccess && over > 0.f) ms -= std::min(over, ms);
+        float over = 0.f;  // part of [a, b] that lies before the latest end seen so far
+        if (ds.last_end && hipEventElapsedTime(&over, p.a, ds.last_end) == hipSuccess && over > 0.f) ms -= std::min(over, ms);
+        float behind = 0.f;  // a pair of another stream may end before it
+        if (!ds.last_end || hipEventElapsedTime(&behind, ds.last_end, p.b) != hipSuccess || behind > 0.f) latest = p.b;
         (void)hipGetLastError();
         g_acc[p.kid].launches += 1;
         g_acc[p.kid].ms += ms;
@@ -81,9 +84,9 @@ void fold(const Pair& p) {
         (void)hipGetLastError();
     }
     ds.free_events.push_back(p.a);
-    if (ds.last_end) ds.free_events.push_back(ds.last_end);
-    ds.last_end = p.b;  // kept until the next pair of this device has been folded
-    ds.last_stream = p.stream;
+    if (latest != p.b) ds.free_events.push_back(p.b);
+    else if (ds.last_end) ds.free_events.push_back(ds.last_end);
+    ds.last_end = latest;  // kept until a later end of this device has been folded
 }
 
 __global__ __launch_bounds__(256) void k_kt_attn_work(const int32_t* __restrict__ cu, int32_t n_seqs, unsigned long long hidden,
@@ -121,7 +124,7 @@ KtScope::~KtScope() {
     if (!a) return;
     std::lock_guard<std::mutex> lk(g_mu);
     hipEvent_t b = get_event(dev);
-    if (b && hipEventRecord(b, (hipStream_t)st) == hipSuccess) g_pending.push_back(Pair{(hipEvent_t)a, b, kid, dev, work, st});
+    if (b && hipEventRecord(b, (hipStream_t)st) == hipSuccess) g_pending.push_back(Pair{(hipEvent_t)a, b, kid, dev, work});
     else {
         (void)hipGetLastError();
         g_dev[dev].free_events.push_back((hipEvent_t)a);

@@ -87,6 +87,23 @@ class RecomputeProvider:
             _lib.check(_lib.load().lm_recompute_get_stats(self._native, C.byref(st)), "lm_recompute_get_stats")
         return {n: int(getattr(st, n)) for n, _ in _lib.RecomputeStats._fields_}
 
+    def set_native_option(self, name: str, value: int) -> None:
+        """An option of the library-side provider (include/leann_mi355x.h: "lanes" = forwards in flight, 1..3; "lane_min_tokens")."""
+        from . import _lib
+
+        if self.native() is None:
+            raise _lib.LeannMi355xError("this model / token store has no library-side recompute provider")
+        _lib.check(_lib.load().lm_recompute_set_option(self._native, name.encode(), int(value)), "lm_recompute_set_option")
+
+    def get_native_option(self, name: str) -> int:
+        from . import _lib
+
+        if self.native() is None:
+            raise _lib.LeannMi355xError("this model / token store has no library-side recompute provider")
+        v = C.c_int64()
+        _lib.check(_lib.load().lm_recompute_get_option(self._native, name.encode(), C.byref(v)), "lm_recompute_get_option")
+        return int(v.value)
+
     @property
     def chunks(self) -> int:
         """Chunks encoded since the counter was last reset (both forms)."""
