@@ -99,8 +99,10 @@ def test_real_leann_searcher_on_top_of_the_backend(tmp_path, built_libs):
     LEANN checkout (in this repo's dev container: /root/reference/packages/leann-core/src)."""
     import sys
 
-    ref = Path("/root/reference/packages/leann-core/src")
-    if ref.is_dir() and str(ref) not in sys.path:
+    from tests.util import leann_core_src
+
+    ref = leann_core_src()
+    if ref is not None and str(ref) not in sys.path:
         sys.path.insert(0, str(ref))
     try:
         from leann.api import LeannSearcher

@@ -1,7 +1,20 @@
 """Shared fixtures for the parity tests: seeded synthetic corpora + graphs."""
 from __future__ import annotations
 
+from pathlib import Path
+
 import numpy as np
+
+REF_CORE = Path("/root/reference/packages/leann-core/src")
+
+
+def leann_core_src():
+    """The reference checkout's leann-core sources, or None where this user cannot see them: the tree is absent, or it lies under a
+    directory that the user running the tests may not enter (Path.exists() raises PermissionError there instead of answering False)."""
+    try:
+        return REF_CORE if (REF_CORE / "leann" / "api.py").exists() else None
+    except OSError:
+        return None
 
 
 def clustered(n: int, d: int, seed: int, n_centers: int = 64, sigma: float = 0.4, normalize: bool = True):
