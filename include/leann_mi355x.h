@@ -635,13 +635,16 @@ size_t lm_pq_train_workspace_bytes(int64_t s, int32_t d, int32_t m);
 int lm_add_layernorm_f16(const void *d_x, const void *d_residual, const void *d_gamma, const void *d_beta,
                          void *d_out, int64_t rows, int32_t hidden, float eps, void *stream);
 
-/* Fused self-attention for packed variable-length sequences, head_dim 32 (hidden = heads*32), lengths 1..256:
+/* Fused self-attention for packed variable-length sequences, head_dim 32 (hidden = heads*32), lengths 1..512:
  * d_qkv [total_tokens][3][heads][32] fp16 (the QKV GEMM output), d_cu_seqlens int32[n_seqs+1],
- * d_out [total_tokens][heads*32] fp16.  softmax(QK^T/sqrt(32))V per (sequence, head), MFMA 32x32x16 f16. */
+ * d_out [total_tokens][heads*32] fp16.  softmax(QK^T/sqrt(32))V per (sequence, head), MFMA 32x32x16 f16.
+ * max_len <= 256: one kernel (four waves per (sequence, head)).  max_len 257..512 (bge-small's max_seq_length): two kernels over the
+ * same launch -- that one for the sequences of at most 256 tokens, the long form (eight waves, K / V of up to 512 tokens in 64 KB of
+ * LDS) for the others -- so a sequence of at most 256 tokens gets the same bits whatever shares its launch.  max_len > 512: LM_EINVAL. */
 int lm_attn_varlen_hd32_f16(const void *d_qkv, const int32_t *d_cu_seqlens, int32_t n_seqs, int32_t heads,
                             int32_t max_len, void *d_out, void *stream);
 
-/* The same kernel for head_dim 32 or 64 (hidden = heads * head_dim; 64: bge-base / contriever, lengths 1..512; 32: lengths 1..256):
+/* The same kernel for head_dim 32 or 64 (hidden = heads * head_dim; 64: bge-base / contriever; 32: as lm_attn_varlen_hd32_f16; lengths 1..512 at both):
  * d_qkv [total_tokens][3][heads][head_dim] fp16, d_out [total_tokens][heads * head_dim] fp16. */
 int lm_attn_varlen_f16(const void *d_qkv, const int32_t *d_cu_seqlens, int32_t n_seqs, int32_t heads, int32_t head_dim,
                        int32_t max_len, void *d_out, void *stream);
@@ -735,7 +738,8 @@ int lm_gemm_f16(const void *d_x, const void *d_w, const float *d_bias, const voi
  * Replaces compute_embeddings' model.encode() (leann/embedding_compute.py:229-239) for sentence-transformers models of the
  * all-MiniLM family: embedding front end, per layer {lm_gemm_ws_h384_f16 (QKV), lm_attn_varlen_hd32_f16,
  * lm_layer_tail_h384_f16}, lm_meanpool_varlen_f16 / lm_clspool_varlen_f16 -- one foreign-function call per recompute round
- * instead of ~3 L + 2.  ffn a multiple of 192 in [192, 1728] (other widths: lm_bert_forward_packed).
+ * instead of ~3 L + 2.  ffn a multiple of 192 in [192, 1728] (other widths: lm_bert_forward_packed).  max_len 1..512 (above 256 -- bge-small's
+ * 512-token chunks -- the QKV projection writes [tokens][1152] and attention takes its long form: lm_attn_varlen_hd32_f16).
  * All pointers are device pointers except `layers` (host array).  Weight layouts as documented at the entry points named above
  * (the three images of lm_layer_tail_pack_h384; leann_amd/encoder.py: pack_tail_images).  d_out: fp32 [n_seqs][384]. */
 typedef struct lm_bert_h384_layer {
@@ -793,7 +797,7 @@ int lm_bert_h384_forward_packed(const lm_bert_h384 *m, const int32_t *d_tok, con
  * lm_gemm_f16 (+ residual) | lm_add_layernorm_f16}, lm_meanpool_varlen_f16 / lm_clspool_varlen_f16 -- the launch sequence of
  * leann_amd/encoder.py: EncoderLayer._forward_packed_general, as one foreign-function call.  Weights are the nn.Linear tensors
  * themselves (fp16 [n_out][k_in], biases fp32, LayerNorm parameters fp16).  Envelope: hidden % 128 == 0 and <= 768, ffn % 128 == 0,
- * head_dim = hidden / heads = 32 (chunk lengths <= 256) or 64 (<= 512).  d_out: fp32 [n_seqs][hidden]. */
+ * head_dim = hidden / heads = 32 or 64, chunk lengths <= 512.  d_out: fp32 [n_seqs][hidden]. */
 typedef struct lm_bert_layer {
     const void *wqkv;  /* [3 hidden][hidden] */
     const float *bqkv;
@@ -841,10 +845,10 @@ int64_t lm_tokens_count(const lm_tokens *t);
  * model.encode() (hnsw_embedding_server.py:148-284, leann/api.py:203-215, leann/embedding_compute.py:229-239) -- as library code:
  * ids -> token store -> packed forward -> fp32 [n][hidden], no interpreter in the search loop.  `model` (the struct and its `layers`
  * array are copied; the device weights they point to must outlive the handle) and `tokens` as above; chunks are truncated to
- * max_seq_len (1..256) tokens; a call with more than max_tokens_per_forward tokens runs as several forwards (bounds by cumulative
+ * max_seq_len (1..512) tokens; a call with more than max_tokens_per_forward tokens runs as several forwards (bounds by cumulative
  * token count, as leann_amd/encoder.py: encode_tokens_packed cuts them).  Envelope: lm_bert_h384_forward_packed's
  * (lm_recompute_create: hidden 384, the fused kernels) or lm_bert_forward_packed's (lm_recompute_create_general: e.g. bge-base,
- * 768-d; max_seq_len up to 512 at head_dim 64); the embeddings are fp32 [n][hidden].
+ * 768-d); the embeddings are fp32 [n][hidden].
  *   lm_index_set_recompute(idx, rc)  attaches it as the index's embedding provider (NULL detaches) and lets the search loop
  *                                    compute the round's chunk lengths before its own per-round device-to-host copy: ONE host
  *                                    synchronisation per round (lm_index_set_provider with a foreign callback: the callback's own);

@@ -233,7 +233,8 @@ static int attn_v2_launch_hd(const void* d_qkv, const int32_t* d_cu_seqlens, int
     if constexpr (HD == 32) {  // generation 3 (lm_attn_v3.hip) is the default at head_dim 32 since round 5; LEANN_MI355X_ATTN=2 = this file's kernel (A/B)
         const char* gen = getenv("LEANN_MI355X_ATTN");
         const char* var = getenv("LEANN_MI355X_ATTN3");  // (9 = generation 2 as well: a switch that leaves the one-call forwards on, for A/B runs of bench.py)
-        if (!(gen && gen[0] == '2') && !(var && var[0] == '9')) return lm_attn_v3_launch_hd32(d_qkv, d_cu_seqlens, n_seqs, heads, max_len, d_out, 0, stream);
+        // (above 256 tokens there is one kernel: the long form in lm_attn_v3.hip)
+        if (max_len > 256 || (!(gen && gen[0] == '2') && !(var && var[0] == '9'))) return lm_attn_v3_launch_hd32(d_qkv, d_cu_seqlens, n_seqs, heads, max_len, d_out, 0, stream);
     }
     const int nt = (max_len + 31) / 32;
     const size_t shmem = ((size_t)32 * nt * (HD + 8) + (size_t)HD * (32 * nt + 4)) * 2;
@@ -263,7 +264,7 @@ static int attn_v2_launch_hd(const void* d_qkv, const int32_t* d_cu_seqlens, int
                     default: LM_FAIL(LM_EINVAL, "lm_attn_varlen_f16 (head_dim 64) supports sequence lengths 1..512");
                 }
             } else {
-                LM_FAIL(LM_EINVAL, "lm_attn_varlen_hd32_f16 supports sequence lengths 1..256");
+                LM_FAIL(LM_EINVAL, "lm_attn_varlen_hd32_f16: generation 2 supports sequence lengths 1..256");
             }
 #undef CASEA
     }
@@ -275,7 +276,7 @@ extern "C" int lm_attn_varlen_hd32_f16(const void* d_qkv, const int32_t* d_cu_se
                                        void* d_out, void* stream) {
     if (n_seqs == 0) return LM_OK;
     if (!d_qkv || !d_cu_seqlens || !d_out || n_seqs < 0 || heads <= 0) LM_FAIL(LM_EINVAL, "bad attention arguments");
-    if (max_len <= 0 || max_len > 256) LM_FAIL(LM_EINVAL, "lm_attn_varlen_hd32_f16 supports sequence lengths 1..256");
+    if (max_len <= 0 || max_len > 512) LM_FAIL(LM_EINVAL, "lm_attn_varlen_hd32_f16 supports sequence lengths 1..512");
     return attn_v2_launch_hd<32>(d_qkv, d_cu_seqlens, n_seqs, heads, max_len, d_out, stream);
 }
 
@@ -284,7 +285,7 @@ extern "C" int lm_attn_varlen_f16(const void* d_qkv, const int32_t* d_cu_seqlens
     if (n_seqs == 0) return LM_OK;
     if (!d_qkv || !d_cu_seqlens || !d_out || n_seqs < 0 || heads <= 0 || max_len <= 0) LM_FAIL(LM_EINVAL, "bad attention arguments");
     if (head_dim == 32) {
-        if (max_len > 256) LM_FAIL(LM_EINVAL, "lm_attn_varlen_f16 (head_dim 32) supports sequence lengths 1..256");
+        if (max_len > 512) LM_FAIL(LM_EINVAL, "lm_attn_varlen_f16 (head_dim 32) supports sequence lengths 1..512");
         return attn_v2_launch_hd<32>(d_qkv, d_cu_seqlens, n_seqs, heads, max_len, d_out, stream);
     }
     if (head_dim == 64) {

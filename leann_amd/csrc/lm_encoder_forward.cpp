@@ -89,7 +89,7 @@ int lm::bert_h384_forward_planned(const lm_bert_h384* m, const int32_t* d_tok, c
     if (!m || !m->layers || !d_tok || !d_pos || !d_cu_seqlens || !d_workspace || !d_out || n_seqs < 0 || total_tokens < 0)
         LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: bad arguments");
     if (!bert_h384_envelope_ok(m->n_layers, m->heads, m->ffn)) LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: needs " LM_BERT_H384_ENVELOPE_TEXT);
-    if (max_len <= 0 || max_len > 256) LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: sequence lengths 1..256");
+    if (max_len <= 0 || max_len > 512) LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: sequence lengths 1..512");
     if (m->pooling != 0 && m->pooling != 1) LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: pooling 0 (mean) or 1 (CLS)");
     if (workspace_bytes < lm_bert_h384_workspace_bytes(total_tokens)) LM_FAIL(LM_EINVAL, "lm_bert_h384_forward_packed: workspace too small");
     const size_t row = (size_t)total_tokens * 384 * 2;
@@ -169,7 +169,7 @@ extern "C" int lm_bert_forward_packed(const lm_bert* m, const int32_t* d_tok, co
     if (!d_tok || !d_pos || !d_cu_seqlens || !d_workspace || !d_out || n_seqs < 0 || total_tokens < 0)
         LM_FAIL(LM_EINVAL, "lm_bert_forward_packed: bad arguments");
     const int32_t H = m->hidden, hd = H / m->heads;
-    if (max_len <= 0 || max_len > (hd == 32 ? 256 : 512)) LM_FAIL(LM_EINVAL, "lm_bert_forward_packed: sequence lengths 1..256 (head_dim 32) / 1..512 (head_dim 64)");
+    if (max_len <= 0 || max_len > 512) LM_FAIL(LM_EINVAL, "lm_bert_forward_packed: sequence lengths 1..512");
     if (workspace_bytes < lm_bert_workspace_bytes(m, total_tokens)) LM_FAIL(LM_EINVAL, "lm_bert_forward_packed: workspace too small");
     const size_t row = (size_t)total_tokens * H * 2;
     unsigned char* ws = (unsigned char*)d_workspace;

@@ -166,8 +166,9 @@ int bert_h384_forward_planned(const lm_bert_h384* m, const int32_t* d_tok, const
 // lm_qkv_h384.hip: lm_qkv_h384_f16 with the output layout as a parameter: 0 = [tokens][n_out] (the C ABI's), 1 = head major [n_out / 32][tokens][32]
 int lm_qkv_h384_launch(const void* d_x, const void* d_w_img, const float* d_bias, int32_t n_out, void* d_out, int64_t tokens, int32_t head_major, void* stream);
 
-// lm_attn_v3.hip: generation 3 of the head_dim-32 attention kernel (arguments as lm_attn_varlen_hd32_f16; max_len 1..256 checked by the caller).
-// total_tokens > 0: qkv is lm_qkv_h384_launch's HEAD-MAJOR layout over that many tokens ([3 x heads][total_tokens][32]); 0 = [tokens][3 x heads x 32]
+// lm_attn_v3.hip: generation 3 of the head_dim-32 attention kernel (arguments as lm_attn_varlen_hd32_f16; max_len 1..256) and, for
+// max_len 257..512, that kernel for the launch's short sequences plus its long form for the others.
+// total_tokens > 0 (max_len <= 256 only): qkv is lm_qkv_h384_launch's HEAD-MAJOR layout over that many tokens ([3 x heads][total_tokens][32]); 0 = [tokens][3 x heads x 32]
 int lm_attn_v3_launch_hd32(const void* d_qkv, const int32_t* d_cu_seqlens, int32_t n_seqs, int32_t heads, int32_t max_len, void* d_out, int64_t total_tokens,
                            void* stream);
 

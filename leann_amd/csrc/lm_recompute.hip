@@ -461,7 +461,7 @@ int lm_recompute_create(const lm_bert_h384* model, const lm_tokens* tokens, int3
     if (!model || !model->layers || !tokens) LM_FAIL(LM_EINVAL, "lm_recompute_create: NULL model / token store");
     if (!bert_h384_envelope_ok(model->n_layers, model->heads, model->ffn))
         LM_FAIL(LM_EINVAL, "lm_recompute_create: needs " LM_BERT_H384_ENVELOPE_TEXT " (the one-call forward's envelope; other shapes: lm_recompute_create_general)");
-    if (max_seq_len <= 0 || max_seq_len > 256) LM_FAIL(LM_EINVAL, "lm_recompute_create: chunk length limit must be 1..256 tokens");
+    if (max_seq_len <= 0 || max_seq_len > 512) LM_FAIL(LM_EINVAL, "lm_recompute_create: chunk length limit must be 1..512 tokens");
     if (max_tokens_per_forward <= 0) LM_FAIL(LM_EINVAL, "lm_recompute_create: max_tokens_per_forward must be positive");
     LM_HIP(hipSetDevice(tokens->device));
     lm_recompute* rc = new lm_recompute();
@@ -481,8 +481,7 @@ int lm_recompute_create_general(const lm_bert* model, const lm_tokens* tokens, i
         model->heads <= 0 || (model->heads * 32 != model->hidden && model->heads * 64 != model->hidden) || (model->pooling != 0 && model->pooling != 1))
         LM_FAIL(LM_EINVAL, "lm_recompute_create_general: outside lm_bert_forward_packed's envelope (hidden % 128 == 0 and <= 768, ffn % 128 == 0, "
                            "head_dim 32 or 64, mean or CLS pooling)");
-    if (max_seq_len <= 0 || max_seq_len > (model->heads * 32 == model->hidden ? 256 : 512))
-        LM_FAIL(LM_EINVAL, "lm_recompute_create_general: chunk length limit must be 1..256 tokens (head_dim 32) / 1..512 (head_dim 64)");
+    if (max_seq_len <= 0 || max_seq_len > 512) LM_FAIL(LM_EINVAL, "lm_recompute_create_general: chunk length limit must be 1..512 tokens");
     if (max_tokens_per_forward <= 0) LM_FAIL(LM_EINVAL, "lm_recompute_create_general: max_tokens_per_forward must be positive");
     LM_HIP(hipSetDevice(tokens->device));
     lm_recompute* rc = new lm_recompute();

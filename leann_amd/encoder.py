@@ -180,15 +180,15 @@ def fused_add_layernorm(x: torch.Tensor, residual: Optional[torch.Tensor], ln: n
 
 
 def fused_attention_hd32(qkv: torch.Tensor, cu: torch.Tensor, heads: int, max_len: int) -> Optional[torch.Tensor]:
-    """Hand-written MFMA varlen attention (csrc/lm_attn_v2.hip) for head_dim 32 (lengths <= 256) and head_dim 64 (lengths <= 512),
-    fp16 on the GPU; returns None when the shape is outside that envelope (caller falls back to torch's varlen_attn)."""
+    """Hand-written MFMA varlen attention (csrc/lm_attn_v3.hip, lm_attn_v2.hip) for head_dim 32 and 64, lengths <= 512, fp16 on the
+    GPU; returns None when the shape is outside that envelope (caller falls back to torch's varlen_attn)."""
     import os
 
     tot, h3 = qkv.shape
     hidden = h3 // 3
     hd = hidden // heads if heads else 0
-    if not (qkv.is_cuda and qkv.dtype == torch.float16 and qkv.is_contiguous() and hidden == heads * hd and (
-            (hd == 32 and 0 < max_len <= 256) or (hd == 64 and 0 < max_len <= 512))):
+    if not (qkv.is_cuda and qkv.dtype == torch.float16 and qkv.is_contiguous() and hidden == heads * hd
+            and hd in (32, 64) and 0 < max_len <= 512):
         return None
     if os.environ.get("LEANN_MI355X_ATTN", "1") == "0":  # torch's varlen_attn (A/B)
         return None
@@ -798,7 +798,7 @@ class BertEncoder(nn.Module):
         kernels as the per-kernel path below, strung together on the C++ side, so a recompute round costs one ctypes call instead of
         ~3 L + 2.  Default since round 3 (measured on an MI355X, 200k-chunk index: B = 1 p50 57.7 -> 56.3 ms, B = 4 68.2 -> 66.8 ms;
         bit-identical results); LEANN_MI355X_ONECALL=0 = the per-kernel path (A/B).  Applies to hidden 384 = heads x 32, fp16, mean
-        pooling, lengths <= 256, no kernel-selection switch set (KERNEL_SELECTION_KEYS), no per-kernel timers running.  None = not
+        pooling, lengths <= 512, no kernel-selection switch set (KERNEL_SELECTION_KEYS), no per-kernel timers running.  None = not
         applicable: the caller takes the per-kernel path (logged once per reason)."""
         import os
 
@@ -816,9 +816,9 @@ class BertEncoder(nn.Module):
 
         lib = _lib.load()
         tot, n = tok.shape[0], cu.shape[0] - 1
-        pk = self.onecall_model() if max_len <= 256 else None
+        pk = self.onecall_model()
         if pk is None:  # other widths (768: bge-base, contriever): the general kernels, also strung together on the C++ side
-            gk = self.general_model() if max_len <= (256 if self.cfg.hidden == self.cfg.heads * 32 else 512) else None
+            gk = self.general_model()
             if gk is None:
                 return None
             need = int(lib.lm_bert_workspace_bytes(C.byref(gk["model"]), tot))

@@ -58,7 +58,7 @@ class RecomputeProvider:
                 or KernelTimers.active is not None or any(k in os.environ for k in KERNEL_SELECTION_KEYS)):
             return None
         cfg = self.encoder.cfg
-        fused = cfg.hidden == 384 and self.T <= 256
+        fused = cfg.hidden == 384
         # cached packs; a NEW pack object means the weights changed: the handle holds the old pointers
         pk = self.encoder.onecall_model() if fused else None
         if pk is None:
@@ -67,8 +67,7 @@ class RecomputeProvider:
             return self._native
         self.close()
         self._native_tried, self._native_pack = True, pk
-        t_max = 256 if cfg.heads and cfg.hidden == cfg.heads * 32 else 512
-        if pk is None or not (0 < self.T <= t_max) or self.dp != cfg.hidden or not self.encoder.word.weight.is_cuda:
+        if pk is None or not (0 < self.T <= 512) or self.dp != cfg.hidden or not self.encoder.word.weight.is_cuda:
             return None
         from . import _lib
 
