@@ -92,7 +92,7 @@ int lm_index_create_from_csr(int64_t ntotal, int32_t d, int32_t metric,
  * Option "persistent_wave": -1 (auto) and 0 give the 256-thread workgroup per query (a view knows no mean degree), 1 the wave per
  * query; both give the same bits.
  * LM_EINVAL at creation, no handle returned: NULL levels or out; n_levels < 1; ntotal < 0 or > INT32_MAX; an unsupported d (the
- * widths the search kernels cover: d padded to 64..384, 512, 768, 1024) or metric; a level with cap < 1, n_rows < 0 or
+ * widths a view covers: d padded to 64..384, 512, 768, 1024 -- not the wide widths of lm_index_search) or metric; a level with cap < 1, n_rows < 0 or
  * n_rows > ntotal; level 0 not the identity level; an upper level with n_rows > 0 and NULL d_nodes (unless n_rows == ntotal: the
  * identity); NULL d_adj with n_rows > 0; entry_point outside [0, ntotal) when ntotal > 0.  ntotal == 0 gives a valid handle whose
  * searches fill the empty values.  lm_index_free frees the handle, never the level arrays. */
@@ -109,7 +109,8 @@ void lm_index_free(lm_index *idx);
 typedef struct {
     int64_t ntotal;
     int32_t d;
-    int32_t d_padded;       /* row stride of embeddings handed to the kernels (multiple of 64) */
+    int32_t d_padded;       /* row stride of embeddings handed to the kernels: d rounded up to a multiple of 64 and, from 1536 on, to
+                               the next wide width (1536, 2048, 2560, 3072, 4096: d in 1473..1536 gives 1536, 1537..2048 gives 2048, ...) */
     int32_t metric;
     int32_t entry_point;
     int32_t max_level;
@@ -195,7 +196,19 @@ void lm_search_params_default(lm_search_params *p);
  * and "update_variant" 0) needs (2 * max(efSearch, k) + P(maxnew)) * 8 + 4 * maxnew <= 150 KiB of LDS; every other search, and that
  * one where it needs more, runs the lock-step rounds, which need (2 * max(efSearch, k) + P(maxnew)) * 8 <= 64 KiB.  What fits neither
  * is LM_EINVAL (lm_last_error names the LDS), decided in 64-bit arithmetic before the search workspace is allocated or anything is launched: the
- * outputs are untouched and the handle serves the next call.  That covers any beam_size and batch_size up to INT32_MAX. */
+ * outputs are untouched and the handle serves the next call.  That covers any beam_size and batch_size up to INT32_MAX.
+ * Widths: d_padded in 64..384, 512, 768, 1024, and the WIDE widths 1536, 2048, 2560, 3072, 4096 (OpenAI text-embedding-3 / ada-002,
+ * Qwen3-Embedding 4B / 8B); any other width is LM_EINVAL ("unsupported padded dimension"), before anything is staged or launched.  A wide
+ * index is served by lm_index_search*, recompute 0 (fp32 / fp16 table) and 1 (provider rows fp32 [n][d_padded], memo and hub cache
+ * included), by lm_index_search_exact* and, for its rows, by lm_exact_search and lm_dist_gather.  Its kernels keep the query in LDS and
+ * are the 256-thread forms (options "persistent_wave" 1 and "update_variant" 3 are accepted and served by them: the same bits), so the
+ * LDS rules carry 4 * d_padded bytes more, with P(maxnew) at least 2:
+ *     persistent launch  (2 * max(efSearch, k) + P(maxnew)) * 8 + 4 * maxnew + 4 * d_padded <= 150 KiB, else the lock-step rounds:
+ *     lock-step rounds   (2 * max(efSearch, k) + P(maxnew)) * 8 + 4 * d_padded <= 64 KiB,
+ * and what fits neither is LM_EINVAL as above.  NOT served at a wide width, LM_EINVAL before anything is staged or launched and with the
+ * outputs untouched: lm_index_create_view (hence lm_graph_insert_batch), lm_select_neighbors, lm_graph_add_links, lm_graph_prune_hubs,
+ * lm_index_search_filtered*, pq_pruning_ratio > 0, lm_pq_attach* and every lm_pq_* search on such an index.  The graph of a wide table
+ * is built on the host. */
 int lm_index_search(lm_index *idx, int64_t n, const float *x, int32_t k, float *distances,
                     int64_t *labels, const lm_search_params *params);
 /* Same with queries and results resident in HBM (no PCIe in the timed region). */
@@ -286,7 +299,8 @@ int lm_pq_batch_search_device(lm_index *idx, int64_t n, const float *d_x, int32_
 
 /* ---- stand-alone kernels (parity tests, shard merge) ----------------------------------------
  * Distances of query row qidx[i] against embedding row ids[i] with the canonical reduction of
- * oracle/lm_oracle.c:orc_dist.  d_table rows have stride d_padded; d_q is nq x d_padded. */
+ * oracle/lm_oracle.c:orc_dist.  d_table rows have stride d_padded; d_q is nq x d_padded.  d_padded: 64..384, 512, 768, 1024 and the wide
+ * widths 1536, 2048, 2560, 3072, 4096 (the same bits from their block-streamed form); any other is LM_EINVAL. */
 int lm_dist_gather(const void *d_table, int32_t dtype, int32_t d_padded, int32_t metric,
                    const float *d_q, const int32_t *d_qidx, const int32_t *d_ids, int64_t npairs,
                    float *d_out, void *stream);
@@ -308,7 +322,8 @@ int lm_topk_merge(const int64_t *d_in_ids, const float *d_in_dist, int32_t S, in
  * occlude_list): scan the candidates not yet kept, in order, while fewer than m are kept, with thr[j] in place of d_dist[j], tested
  * against everything kept so far; a2 = alpha * alpha in fp32, thr = d / a2 (L2), thr = -(1.0f - (1.0f + d) / a2) (inner product of
  * unit vectors).  fp32 throughout, no contraction.
- * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width the search kernels do not cover, K < 1 or K > LM_SELECT_MAX_K,
+ * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width other than 64..384, 512, 768, 1024 (the wide widths of
+ * lm_index_search are not covered: "unsupported padded dimension"), K < 1 or K > LM_SELECT_MAX_K,
  * m < 1, alpha < 1 or not finite, n < 0.  n == 0: LM_OK.
  * LM_SELECT_MAX_K: the kept set is a K-bit mask in registers.  The batched builder reaches K = k_cand + 1 + cap = 193 at M = 32
  * (257 at M = 64) when it refines level 0, and 2 cap = 128 when it shrinks an overflowing list. */
@@ -463,7 +478,10 @@ int lm_graph_insert_batch(lm_index *view, const int32_t *d_batch, int64_t b, int
  * s0 = clamp(ceil(ntable / 1024), 1, max(1, 512 / nqt)); rows per slice = max(32, ceil(ntable / s0) rounded up to a multiple of 32);
  * S = max(1, ceil(ntable / rows)) slices.  One query: ntable <= 1024 is one slice, 1025..2048 two, 20000 twenty (the last of 544 rows).
  * The workspace holds the S partial lists per query: lm_exact_search_workspace_bytes = S * nq * k * 8.
- * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width the search kernels do not cover, unknown dtype or metric, k < 1 or
+ * Widths: 64..384, 512, 768, 1024, and the wide widths 1536, 2048, 2560, 3072, 4096.  At a wide width a tile's eight queries are scored
+ * in sub-tiles of 8 (up to 2048) or 4 queries, the slice's rows read once per sub-tile (the queries' LDS stays at or under 64 KB); the
+ * slicing policy, the workspace size, labels and distance bits do not depend on it.
+ * LM_EINVAL (before anything is launched): d_padded % 64 != 0 or a width not listed above, unknown dtype or metric, k < 1 or
  * k > LM_EXACT_MAX_K, negative nq / ntable, ntable > INT32_MAX, a NULL buffer where one is needed, workspace_bytes below
  * lm_exact_search_workspace_bytes(ntable, nq, k).  nq == 0: LM_OK.  ntable == 0: every slot gets the empty values. */
 #define LM_EXACT_MAX_K 256

@@ -59,6 +59,13 @@ __device__ __forceinline__ void load_query(const float* Q, int q, int lane16, fl
     for (int i = 0; i < NCH; ++i) qv[i] = qrow[lane16 + 16 * i];
 }
 
+// ---- the wide form of the same distance (d_padded 1536 .. 4096: nch = d_padded / 64 is a run-time multiple of 8), defined in lm_wide_impl.h
+//      at the end of the translation unit: the query sits in LDS (wide_stage_query), ROWS rows stream through registers in blocks of 8 chunks.
+//      The kernels select it with NCH == 0. ----
+__device__ __forceinline__ void wide_stage_query(const float* Q, int64_t q, int nch, float4* sq, int tid, int nt);
+template <bool L2, bool F16, int ROWS>
+__device__ __forceinline__ void wide_dist(const void* table, const int64_t (&slot)[ROWS], const float4* qrow, int nch, int lane16, float (&dist)[ROWS]);
+
 // ---- bitonic sort (ascending) of newk[0 .. Pn), Pn a power of two, by NT cooperating threads; ends with a barrier ----
 template <int NT>
 __device__ __forceinline__ void sort_keys(uint64_t* newk, int Pn, int tid) {

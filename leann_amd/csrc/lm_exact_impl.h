@@ -222,6 +222,9 @@ static int launch_exact_scan(const void* d_table, int64_t ntable, const float* d
 
 }  // namespace lm
 
+static int launch_exact_scan_wide(const void* d_table, bool f16, int64_t ntable, int32_t d_padded, bool l2, const float* d_q, int64_t nq, int32_t k,
+                                  const uint32_t* d_allow, const lm::ExactPlan& p, uint64_t* part, hipStream_t st);  // lm_wide_impl.h
+
 extern "C" {
 
 size_t lm_exact_search_workspace_bytes(int64_t ntable, int64_t nq, int32_t k) {
@@ -234,7 +237,8 @@ int lm_exact_search(const void* d_table, int32_t dtype, int64_t ntable, int32_t 
     if (d_padded <= 0 || d_padded % 64) LM_FAIL(LM_EINVAL, "d_padded must be a positive multiple of 64");
     switch (d_padded / 64) {
         case 1: case 2: case 3: case 4: case 5: case 6: case 8: case 12: case 16: break;
-        default: LM_FAIL(LM_EINVAL, "unsupported padded dimension (supported: 64..384, 512, 768, 1024)");
+        default:
+            if (!wide_width(d_padded)) LM_FAIL(LM_EINVAL, "unsupported padded dimension (supported: 64..384, 512, 768, 1024, 1536, 2048, 2560, 3072, 4096)");
     }
     if (dtype != LM_DTYPE_F32 && dtype != LM_DTYPE_F16) LM_FAIL(LM_EINVAL, "dtype must be f32 or f16");
     if (metric != LM_METRIC_INNER_PRODUCT && metric != LM_METRIC_L2) LM_FAIL(LM_EINVAL, "unknown metric");
@@ -259,6 +263,7 @@ int lm_exact_search(const void* d_table, int32_t dtype, int64_t ntable, int32_t 
         break
     switch (d_padded / 64) {
         GO(1); GO(2); GO(3); GO(4); GO(5); GO(6); GO(8); GO(12); GO(16);
+        default: rc = launch_exact_scan_wide(d_table, f16, ntable, d_padded, l2, d_q, nq, k, d_allow, p, part, st);  // (lm_wide_impl.h)
     }
 #undef GO
     if (rc) return rc;

@@ -11,6 +11,7 @@ namespace lm {
 // beam with the same pop / visited / merge rules as k_expand + k_update (set semantics => identical results) --
 // keeping pool, frontier and new-list in LDS.  One launch per batch, no host round trips, no launch gaps.
 // dynamic LDS: lpool[ef] | out[ef] | newk[Pmax] (u64) | s_new[maxnew] (i32)
+// (NCH == 0, the wide form of lm_wide_impl.h: lpool | out | newk[Pmax >= 2] | query[16 nch] (float4) | s_new)
 struct PersistArgs {
     const float* Q;
     const void* E;
@@ -18,6 +19,7 @@ struct PersistArgs {
     int64_t* labels;
     float* dist;
     int32_t* rounds_q;
+    int32_t nch;  // NCH == 0 only: d_padded / 64
 };
 
 // NT = threads per query: 256 (a workgroup of 4 waves; long new-lists: high degree x beam) or 64 (ONE wave per query: the
@@ -46,8 +48,15 @@ __global__ __launch_bounds__(NT) void k_search_table(GA g, WsDev ws, PersistArgs
     int32_t* s_new = (int32_t*)(newk + a.Pmax);
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int lane16 = tid & 15, sg = tid >> 4;
-    float4 qv[NCH];
-    load_query<NCH>(a.Q, q, lane16, qv);
+    float4 qv[NCH > 0 ? NCH : 1];
+    const float4* sq = nullptr;
+    if constexpr (NCH == 0) {  // (the first barrier below, in front of the seed's eval_new, publishes the query)
+        sq = (const float4*)s_new;
+        s_new = (int32_t*)(sq + 16 * a.nch);
+        wide_stage_query(a.Q, q, a.nch, (float4*)(newk + a.Pmax), tid, NT);
+    } else {
+        load_query<NCH>(a.Q, q, lane16, qv);
+    }
     uint32_t* vis = ws.visited + (size_t)q * ws.nw;
     unsigned long long ndis = 0;
     int rounds = 0, nsteps = 0;
@@ -59,11 +68,20 @@ __global__ __launch_bounds__(NT) void k_search_table(GA g, WsDev ws, PersistArgs
             const bool has2 = i2 < n;
             const int32_t v0 = s_new[i];
             const int32_t v1 = has2 ? s_new[i2] : v0;
-            float4 e0[NCH], e1[NCH];
-            load_row<NCH, F16>(a.E, (int64_t)v0, lane16, e0);
-            load_row<NCH, F16>(a.E, (int64_t)v1, lane16, e1);
-            const float d0 = row_reduce<NCH, L2>(e0, qv);
-            const float d1 = row_reduce<NCH, L2>(e1, qv);
+            float d0, d1;
+            if constexpr (NCH == 0) {
+                const int64_t slot[2] = {v0, v1};
+                float d[2];
+                wide_dist<L2, F16, 2>(a.E, slot, sq, a.nch, lane16, d);
+                d0 = d[0];
+                d1 = d[1];
+            } else {
+                float4 e0[NCH], e1[NCH];
+                load_row<NCH, F16>(a.E, (int64_t)v0, lane16, e0);
+                load_row<NCH, F16>(a.E, (int64_t)v1, lane16, e1);
+                d0 = row_reduce<NCH, L2>(e0, qv);
+                d1 = row_reduce<NCH, L2>(e1, qv);
+            }
             if (lane16 == 0) {
                 newk[i] = make_key(d0, v0);
                 if (has2) newk[i2] = make_key(d1, v1);

@@ -15,10 +15,11 @@ struct UpdateArgs {
     int32_t max_level;
     int32_t P2;           // k_pq_rerank only: pow2 >= candidates per query
     unsigned long long* tstamp;  // profiling: 2 x B wall-clock stamps (NULL = off)
+    int32_t nch;          // NCH == 0 (the wide form, lm_wide_impl.h) only: d_padded / 64
 };
 
 // sort only the NEW keys, then merge with the (already sorted) pool by rank
-// LDS: pool[ef] | out[ef] | newk[Pmax]
+// LDS: pool[ef] | out[ef] | newk[Pmax]   (NCH == 0, the wide form: | query[16 nch] float4 behind them, Pmax = max(P(maxnew), 2) keeps it 16-byte aligned)
 template <int NCH, bool L2, bool F16, int MODE, int NT>  // MODE 0: row = node id (table), 1: rank in the round's unique list, 2: memo slot
 __device__ __forceinline__ void update_body(const WsDev& ws, const UpdateArgs& a) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -43,8 +44,17 @@ __device__ __forceinline__ void update_body(const WsDev& ws, const UpdateArgs& a
     if (tid == 0) s_best = KEY_NONE;
 
     const int lane16 = tid & 15, sg = tid >> 4;
-    float4 qv[NCH];
-    load_query<NCH>(a.Q, q, lane16, qv);
+    float4 qv[NCH > 0 ? NCH : 1];
+    const float4* sq = nullptr;
+    if constexpr (NCH == 0) {
+        int Pmax = 2;
+        while (Pmax < ws.maxnew) Pmax <<= 1;
+        sq = (const float4*)(newk + Pmax);
+        wide_stage_query(a.Q, q, a.nch, (float4*)(newk + Pmax), tid, NT);
+        __syncthreads();
+    } else {
+        load_query<NCH>(a.Q, q, lane16, qv);
+    }
     const int32_t* newid = ws.newid + (size_t)q * ws.maxnew;
     for (int i = sg; i < n; i += NT / 8) {  // two rows in flight per 16-lane group
         const int i2 = i + NT / 16;
@@ -62,11 +72,20 @@ __device__ __forceinline__ void update_body(const WsDev& ws, const UpdateArgs& a
             s0 = ws.memo_slot[v0];
             s1 = ws.memo_slot[v1];
         }
-        float4 e0[NCH], e1[NCH];
-        load_row<NCH, F16>(a.E, s0, lane16, e0);
-        load_row<NCH, F16>(a.E, s1, lane16, e1);
-        float d0 = row_reduce<NCH, L2>(e0, qv);
-        float d1 = row_reduce<NCH, L2>(e1, qv);
+        float d0, d1;
+        if constexpr (NCH == 0) {
+            const int64_t slot[2] = {s0, s1};
+            float d[2];
+            wide_dist<L2, F16, 2>(a.E, slot, sq, a.nch, lane16, d);
+            d0 = d[0];
+            d1 = d[1];
+        } else {
+            float4 e0[NCH], e1[NCH];
+            load_row<NCH, F16>(a.E, s0, lane16, e0);
+            load_row<NCH, F16>(a.E, s1, lane16, e1);
+            d0 = row_reduce<NCH, L2>(e0, qv);
+            d1 = row_reduce<NCH, L2>(e1, qv);
+        }
         if (lane16 == 0) {
             newk[i] = make_key(d0, v0);
             if (has2) newk[i2] = make_key(d1, v1);

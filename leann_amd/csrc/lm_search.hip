@@ -21,6 +21,8 @@
 //                     k_insert_merge, lm_select_impl.h's launch, k_insert_edges, then lm_link_impl.h's launch sequence
 //   lm_view_impl.h    lm_index_create_view: k_search_table's dense-level graph accessor (fixed-capacity level adjacencies searched in place)
 //   lm_pq_flat_impl.h flat PQ-ADC scan of the code array with an allow-list + the PQ path's rerank tail: k_pq_flat_scan, k_pq_flat_merge
+//   lm_wide_impl.h    padded widths 1536 .. 4096: the row distance with the query in LDS and the rows streamed in blocks of 8 chunks (k_update and
+//                     k_search_table take it as NCH == 0), k_dist_pairs_wide, k_exact_scan_wide, and their launchers
 // Algorithm contract: oracle/lm_oracle.c header (set semantics under the (dist,id) total order).
 // Reference call site replaced: index.search(...) leann_backend_hnsw/hnsw_backend.py:241-248.
 #include <algorithm>
@@ -138,6 +140,25 @@ struct lm_index {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_update, ev_expand, ev_provider;
     std::vector<hipEvent_t> ev_pool;
 };
+
+// The wide padded widths (lm_wide_impl.h), served by the searches over stored or provided embeddings, the exact scan and lm_dist_gather.
+static inline bool wide_width(int32_t dp) { return dp == 1536 || dp == 2048 || dp == 2560 || dp == 3072 || dp == 4096; }
+// d -> padded width: the next multiple of 64, and from 1536 on the next wide width (a width that no kernel serves is refused by the search)
+static inline int32_t padded_width(int32_t d) {
+    const int32_t dp = (d + 63) / 64 * 64;
+    if (dp < 1536 || dp > 4096) return dp;
+    return dp <= 2048 ? (dp + 511) / 512 * 512 : dp <= 2560 ? 2560 : dp <= 3072 ? 3072 : 4096;
+}
+#define WIDE_TEXT "unsupported padded dimension (supported: 64..384, 512, 768, 1024; the widths 1536, 2048, 2560, 3072, 4096 by lm_index_search*, lm_index_search_exact*, lm_exact_search and lm_dist_gather only)"
+// entry points without a wide form refuse a wide index before they stage or launch anything
+#define LM_NOT_WIDE(ix, what) \
+    do { \
+        if ((ix) && (ix)->Dp > 1024) LM_FAIL(LM_EINVAL, std::string(WIDE_TEXT) + ": " + (what)); \
+    } while (0)
+static int launch_update_wide(lm_index* ix, lm::UpdateArgs a, bool f16);                                  // lm_wide_impl.h
+static int launch_persist_wide(lm_index* ix, lm::PersistArgs a, const lm::GraphDev& g, size_t shmem);
+static int launch_dist_pairs_wide(const void* d_table, bool f16, int32_t d_padded, bool l2, const float* d_q, const int32_t* d_qidx, const int32_t* d_ids,
+                                  int64_t npairs, float* d_out, hipStream_t st);
 
 // entry points that read the CSR arrays (or state only a CSR index can have) refuse a view before they stage or launch anything
 #define LM_NOT_ON_VIEW(ix, what) \
@@ -336,6 +357,7 @@ static int launch_update_nch(lm_index* ix, const UpdateArgs& a, size_t shmem) {
     // <= ~48 expected new nodes per query per round (beam x mean level-0 degree)
     const bool wave = ix->update_variant == 3 ||
                       (ix->update_variant == 0 && ix->ws.B >= 4096 && ix->ws.W * ix->avg_degree0 <= (double)ix->wave_maxnew);
+    if (wide_width(ix->Dp)) return launch_update_wide(ix, a, F16);  // (256 threads whatever `wave` says)
     switch (ix->Dp / 64) {
 #define CASE(n)                                                                                              \
     case n:                                                                                                  \
@@ -413,6 +435,8 @@ template <bool L2, bool F16, class GA>
 static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GA& g, size_t shmem) {
     dim3 grid(ix->ws.B);
     const bool wave = persist_wave_form(ix);
+    if constexpr (std::is_same<GA, GraphDev>::value)
+        if (wide_width(ix->Dp)) return launch_persist_wide(ix, a, g, shmem);  // (256 threads whatever `wave` says)
     switch (ix->Dp / 64) {
 #define CASEP(n)                                                                                                         \
     case n:                                                                                                              \
@@ -436,6 +460,8 @@ static int launch_persist_nch(lm_index* ix, const PersistArgs& a, const GA& g, s
 
 #define LOCKSTEP_LDS_TEXT "efSearch / beam_size / batch_size too large for the LDS-resident pool (2*max(efSearch,k) + max(beam*max_degree, batch_size + max_degree) keys must fit 64 KiB)"
 
+#define LOCKSTEP_LDS_WIDE_TEXT "efSearch / beam_size / batch_size too large for the LDS-resident pool at a wide width ((2*max(efSearch,k) + P(max(beam*max_degree, batch_size + max_degree))) * 8 + 4 * d_padded bytes must fit 64 KiB)"
+
 // Everything a search on a view refuses, in front of any staging or launch (NULL / range errors of the arguments are left to do_search_device,
 // which reports them for every index alike).
 static int view_checks(const lm_index* ix, int64_t n, int32_t k, const lm_search_params* prm) {
@@ -452,6 +478,15 @@ static int view_checks(const lm_index* ix, int64_t n, int32_t k, const lm_search
     int64_t P = 1;
     while (P < maxnew) P <<= 1;
     if ((2 * (int64_t)std::max(prm->efSearch, k) + P) * 8 + 4 * maxnew > 150 * 1024) LM_FAIL(LM_EINVAL, VIEW_LDS_TEXT);
+    return LM_OK;
+}
+
+// What a search refuses for the index's width, in front of any staging or launch: a width above 1024 that is not a wide one (no kernel), and the
+// two-level search at a wide width (k_prune has no wide form).
+static int width_checks(const lm_index* ix, const lm_search_params* prm) {
+    if (!ix || !prm || ix->Dp <= 1024) return LM_OK;
+    if (!wide_width(ix->Dp)) LM_FAIL(LM_EINVAL, WIDE_TEXT);
+    if (prm->pq_pruning_ratio > 0.0f) LM_NOT_WIDE(ix, "pq_pruning_ratio > 0");
     return LM_OK;
 }
 
@@ -472,7 +507,12 @@ static int search_pass_persistent(lm_index* ix, int32_t B, const float* d_q, int
     a.Q = d_q; a.E = ix->d_table; a.check_rel = prm.check_relative_distance; a.max_level = ix->max_level;
     a.Pmax = next_pow2(ws.maxnew); a.k = k; a.metric = ix->metric; a.labels = d_labels; a.dist = d_dist;
     a.rounds_q = ix->d_pq_rounds.get();
-    const size_t shmem = ((size_t)2 * ef + a.Pmax) * 8 + (size_t)ws.maxnew * 4;
+    const bool wide = wide_width(ix->Dp);
+    if (wide) {  // the query behind the new keys, 16-byte aligned
+        a.Pmax = std::max(a.Pmax, 2);
+        a.nch = ix->Dp / 64;
+    }
+    const size_t shmem = ((size_t)2 * ef + a.Pmax) * 8 + (size_t)ws.maxnew * 4 + (wide ? (size_t)ix->Dp * 4 : 0);
     if (shmem > 150 * 1024) {
         if (ix->view) LM_FAIL(LM_EINVAL, VIEW_LDS_TEXT);  // (view_checks refuses this before anything is staged; there is no lock-step form of a view)
         return 1;  // caller falls back to the lock-step path
@@ -585,7 +625,8 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
     ua.max_level = ix->max_level;
     {
         // dynamic LDS of the update kernel (default launch limit 64 KiB): pool | merged pool | new keys
-        const size_t need = ((size_t)2 * ef + next_pow2(ws.maxnew)) * 8;
+        const size_t need = wide_width(ix->Dp) ? ((size_t)2 * ef + std::max(next_pow2(ws.maxnew), 2)) * 8 + (size_t)ix->Dp * 4
+                                               : ((size_t)2 * ef + next_pow2(ws.maxnew)) * 8;
         if (need > 64 * 1024) LM_FAIL(LM_EINVAL, LOCKSTEP_LDS_TEXT);  // (do_search_device refuses this before anything is allocated: search_lds_checks)
     }
     const int ntiles = (int)((ws.nw + UNIQ_TILE - 1) / UNIQ_TILE);
@@ -702,9 +743,11 @@ static int search_pass(lm_index* ix, int32_t B, const float* d_q, int32_t k, con
 static int search_lds_checks(const lm_index* ix, int32_t k, const lm_search_params& prm, bool persistent, bool* fits_persistent) {
     const int64_t ef = std::max(prm.efSearch, k), W = std::max(prm.beam_size, 1);
     const int64_t maxnew = ws_maxnew(ix, W, prm.pq_pruning_ratio > 0.0f, prm.batch_size);
-    const int64_t keys = 2 * ef + next_pow2_64(maxnew);
-    *fits_persistent = persistent && keys * 8 + 4 * maxnew <= 150 * 1024;
-    if (!*fits_persistent && keys * 8 > 64 * 1024) LM_FAIL(LM_EINVAL, LOCKSTEP_LDS_TEXT);
+    const bool wide = wide_width(ix->Dp);
+    const int64_t keys = 2 * ef + (wide ? std::max<int64_t>(next_pow2_64(maxnew), 2) : next_pow2_64(maxnew));
+    const int64_t query = wide ? 4 * (int64_t)ix->Dp : 0;  // the wide form keeps the query in LDS
+    *fits_persistent = persistent && keys * 8 + 4 * maxnew + query <= 150 * 1024;
+    if (!*fits_persistent && keys * 8 + query > 64 * 1024) LM_FAIL(LM_EINVAL, wide ? LOCKSTEP_LDS_WIDE_TEXT : LOCKSTEP_LDS_TEXT);
     return LM_OK;
 }
 
@@ -716,6 +759,8 @@ static int do_search_device(lm_index* ix, int64_t n, const float* d_x, int32_t k
     if (prm.efSearch <= 0) LM_FAIL(LM_EINVAL, "efSearch must be positive");
     if (prm.batch_size < 0) LM_FAIL(LM_EINVAL, "batch_size must not be negative (0 = no dynamic batching)");
     if (int vrc = view_checks(ix, n, k, &prm)) return vrc;
+    if (flt) LM_NOT_WIDE(ix, "lm_index_search_filtered*");
+    if (int wrc = width_checks(ix, &prm)) return wrc;
     LM_HIP(hipSetDevice(ix->device));
     if (flt) ix->filtered_allowed_evals = 0;
     ix->stats = lm_search_stats{};
@@ -857,7 +902,7 @@ int lm_index_create_from_csr(int64_t ntotal, int32_t d, int32_t metric, const ui
     LM_HIP(hipSetDevice(device));
     lm_index* ix = new lm_index();
     ix->device = device;
-    ix->N = ntotal; ix->D = d; ix->Dp = (d + 63) / 64 * 64; ix->metric = metric;
+    ix->N = ntotal; ix->D = d; ix->Dp = padded_width(d); ix->metric = metric;
     ix->entry_point = ntotal > 0 ? entry_point : -1;
     ix->max_level = max_level;
     ix->n_neighbors = n_neighbors; ix->n_level_ptr = n_level_ptr;
@@ -1208,6 +1253,7 @@ int lm_index_search(lm_index* ix, int64_t n, const float* x, int32_t k, float* d
     if (n == 0) return LM_OK;
     if (!x || !distances || !labels) LM_FAIL(LM_EINVAL, "NULL buffer");
     if (int vrc = view_checks(ix, n, k, params)) return vrc;
+    if (int wrc = width_checks(ix, params)) return wrc;
     LM_HIP(hipSetDevice(ix->device));
     if (int rc = stage_in(ix, x, n, k)) return rc;
     if (int rc = do_search_device(ix, n, ix->d_stage_x.get(), k, ix->d_stage_d.get(), ix->d_stage_l.get(), params)) return rc;
@@ -1222,6 +1268,7 @@ static int filtered_checks(const lm_index* ix, int64_t n, int32_t k, const lm_se
     if (params->batch_size < 0) LM_FAIL(LM_EINVAL, "batch_size must not be negative (0 = no dynamic batching)");
     if (params->pq_pruning_ratio > 0.0f)
         LM_FAIL(LM_EINVAL, "the filtered graph search takes no pq_pruning_ratio: the two-level search does not evaluate every new node exactly");
+    LM_NOT_WIDE(ix, "lm_index_search_filtered*");
     if (n == 0 || ix->N == 0 || ix->entry_point < 0) return LM_OK;  // nothing to walk: LM_OK whatever is attached
     if (params->recompute) {
         if (!ix->provider) LM_FAIL(LM_ESTATE, "recompute requested but no embedding provider is attached");
@@ -1262,6 +1309,7 @@ int lm_dist_gather(const void* d_table, int32_t dtype, int32_t d_padded, int32_t
     dim3 grid((unsigned)((npairs + 15) / 16)), block(256);
     hipStream_t st = (hipStream_t)stream;
     const bool l2 = metric == LM_METRIC_L2, f16 = dtype == LM_DTYPE_F16;
+    if (wide_width(d_padded)) return launch_dist_pairs_wide(d_table, f16, d_padded, l2, d_q, d_qidx, d_ids, npairs, d_out, st);
 #define GO(n)                                                                                                     \
     case n:                                                                                                       \
         if (l2 && f16) hipLaunchKernelGGL((k_dist_pairs<n, true, true>), grid, block, 0, st, d_table, d_q, d_qidx, d_ids, npairs, d_out);        \
@@ -1300,4 +1348,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_link_impl.h"
 #include "lm_prune_impl.h"
 #include "lm_insert_impl.h"
+#include "lm_wide_impl.h"
 
