@@ -460,6 +460,58 @@ int lm_graph_prune_hubs(const void *d_table, int32_t dtype, int32_t d_padded, in
 int lm_graph_insert_batch(lm_index *view, const int32_t *d_batch, int64_t b, int32_t replace, int32_t kk, int32_t m, float alpha,
                           const lm_search_params *params, int32_t *d_adj, float *d_dist, int32_t *d_deg,
                           int32_t *d_cand_out /* [b][K] or NULL */, float *d_cdist_out /* [b][K] or NULL */, uint8_t *d_keep_out /* [b][K] or NULL */);
+/* Index build time: the finished level adjacencies to the compact CSR of lm_index_create_from_csr (the arrays of the reference's
+ * convert_to_csr.py:494-548), device to device, and one level of a CSR back to the fixed-capacity layout.  With these a plain-C host
+ * that built its levels with lm_graph_insert_batch gets the index it can open, search and write to disk.  (csrc/lm_csr_impl.h)
+ * FORWARD, two calls.  The input has the shape of lm_index_create_view: levels[0] the identity level, an upper level's d_nodes strictly
+ * ascending (the caller's promise, not checked), a slot value outside [0, ntotal) empty, holes tolerated.  A row whose node id lies
+ * outside [0, ntotal) is skipped; nothing is dereferenced for it.
+ *   The result is the CSR of lm_index_create_view's equivalence paragraph: node v carries levels 0 .. top(v), top(v) = the highest
+ *   level that lists v; list l of v holds the non-empty slots of v's row at level l in slot order; a level below top(v) that does not
+ *   list v gives an empty list.  In array terms:
+ *     d_levels[v] = top(v) + 1;   d_node_offsets[0] = 0, d_node_offsets[v + 1] - d_node_offsets[v] = d_levels[v] + 1;
+ *     d_level_ptr[d_node_offsets[v] + l] = where list l of v starts in d_neighbors, l < d_levels[v]; the node's last pointer is the
+ *     sentinel and holds the end of its last list; lists follow each other in pointer order without gaps;
+ *     n_level_ptr = d_node_offsets[ntotal], n_neighbors = the number of non-empty slots.
+ *   lm_graph_levels_to_csr_count writes d_levels [ntotal] and d_node_offsets [ntotal + 1], leaves the per-pointer degrees in the
+ *   workspace and makes ONE stream synchronisation, to hand the two sizes to the host.  The caller allocates d_level_ptr [n_level_ptr]
+ *   and d_neighbors [n_neighbors] (both non-NULL, also when n_neighbors is 0) and calls lm_graph_levels_to_csr_fill with the same
+ *   levels, the two arrays _count wrote and the workspace as _count left it, on the same stream: it writes every element of both.
+ *   _fill makes no host synchronisation, no allocation and no device-to-host copy.  No row is read more than once per call.
+ *   Everything is a function of the input bits alone: integer arithmetic, no atomics, no kernel waits for another workgroup, every
+ *   offset is 64-bit (d_level_ptr passes 2^32 at 60 M chunks).
+ *   Workspace: lm_graph_levels_to_csr_workspace_bytes, a pure function of ntotal and the levels' n_rows (it holds one int32 per
+ *   pointer, bounded by 2 * ntotal + the sum of l * levels[l].n_rows); 0 for arguments the calls reject and for ntotal == 0.
+ *   d_workspace must be 8-byte aligned.
+ *   LM_EINVAL (before anything is launched, the buffers untouched): NULL levels; n_levels < 1 or > LM_CSR_MAX_LEVELS; ntotal < 0 or
+ *   > INT32_MAX; a level with cap < 1, n_rows < 0 or n_rows > ntotal; level 0 not the identity level; an upper level with n_rows > 0
+ *   and NULL d_nodes (unless n_rows == ntotal: the identity); NULL d_adj with n_rows > 0; a NULL output or size pointer; a NULL or
+ *   misaligned d_workspace or workspace_bytes below the function above.  ntotal == 0: LM_OK, n_level_ptr = n_neighbors = 0,
+ *   d_node_offsets[0] = 0 is written, no workspace is needed; _fill then does nothing.
+ * BACKWARD, one call: lm_graph_csr_to_level.  Row r of d_adj [n_rows][cap] receives list `level` of node d_nodes[r] (node r when
+ * d_nodes is NULL, then n_rows == ntotal), left-packed, values as stored; the remaining slots get -1; d_deg[r] = the entries written.
+ * A node with d_levels[v] <= level, and a node id outside [0, ntotal), gives an empty row.  A list longer than cap keeps its first cap
+ * entries and its excess is ADDED to *d_overflow (an integer atomic on a counter the caller cleared): the call does not fail, the
+ * length lives on the device.  A pointer pair that is not a list of this CSR (beyond n_level_ptr, descending, past n_neighbors) gives
+ * an empty row and is not dereferenced.  No host synchronisation, allocation or device-to-host copy.
+ *   LM_EINVAL (before anything is launched, the buffers untouched): ntotal < 0 or > INT32_MAX; negative n_level_ptr, n_neighbors or
+ *   n_rows; n_rows > ntotal; level < 0; cap < 1; NULL d_nodes with n_rows != ntotal; with n_rows > 0 a NULL d_node_offsets, d_levels
+ *   or d_adj, NULL d_level_ptr with n_level_ptr > 0, NULL d_neighbors with n_neighbors > 0.  n_rows == 0: LM_OK, nothing is written. */
+#define LM_CSR_MAX_LEVELS 64
+size_t lm_graph_levels_to_csr_workspace_bytes(int64_t ntotal, const lm_graph_level *levels /* host array */, int32_t n_levels);
+int lm_graph_levels_to_csr_count(int64_t ntotal, const lm_graph_level *levels /* host array */, int32_t n_levels,
+                                 int32_t *d_levels /* [ntotal] out */, uint64_t *d_node_offsets /* [ntotal+1] out */,
+                                 void *d_workspace, size_t workspace_bytes,
+                                 int64_t *n_level_ptr, int64_t *n_neighbors /* host, out */, void *stream);
+int lm_graph_levels_to_csr_fill(int64_t ntotal, const lm_graph_level *levels /* host array */, int32_t n_levels,
+                                const int32_t *d_levels, const uint64_t *d_node_offsets,
+                                uint64_t *d_level_ptr /* [n_level_ptr] out */, int32_t *d_neighbors /* [n_neighbors] out */,
+                                void *d_workspace, size_t workspace_bytes, void *stream);
+int lm_graph_csr_to_level(int64_t ntotal, const uint64_t *d_node_offsets, const uint64_t *d_level_ptr, int64_t n_level_ptr,
+                          const int32_t *d_neighbors, int64_t n_neighbors, const int32_t *d_levels, int32_t level,
+                          const int32_t *d_nodes /* NULL = identity */, int64_t n_rows, int32_t cap,
+                          int32_t *d_adj /* [n_rows][cap] out */, int32_t *d_deg /* [n_rows] out or NULL */,
+                          int64_t *d_overflow /* device counter, out or NULL */, void *stream);
 /* Exact top-k over a stored-embedding table = oracle/lm_oracle.c:orc_bruteforce_topk (the paper's IndexFlatIP baseline) plus an allow-list.  The
  * reference has no such path: leann/api.py:785-790 applies metadata_filters AFTER the graph search, so a filtered query returns fewer than top_k
  * hits; here the filter is part of the scan and the result is the best k of the allowed rows.  (csrc/lm_exact_impl.h)

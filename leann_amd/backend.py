@@ -147,7 +147,10 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         kernels; needs ``gpu_select_kernel``, ``gpu_link_kernel`` and ``gpu_search_view``, and builds the same graph byte for byte.
         ``gpu_prune_kernel`` (bool, default False): the pruning runs as one library call on the device
         (lm_graph_prune_hubs, prune_preserving_hubs(pruner="kernel")): in-degrees, hub choice -- ties at the cut go to the lower id --,
-        link weights and the link insertion, instead of numpy / torch ops on the host's copy of the graph."""
+        link weights and the link insertion, instead of numpy / torch ops on the host's copy of the graph.
+        ``gpu_csr_kernel`` (bool, default False): the CSR is assembled on the device (lm_graph_levels_to_csr_count / _fill,
+        build_graph_gpu(assembler="kernel")) and, with ``gpu_prune_kernel``, the pruning takes its rows from the uploaded CSR
+        (lm_graph_csr_to_level) instead of a dense host array; needs ``gpu_search_view``, and gives the same graph byte for byte."""
         from .hnsw_builder import build_hnsw
 
         bp = self.build_params
@@ -158,6 +161,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         search = "view" if bool(bp.get("gpu_search_view", False)) else "csr"
         prune_kernel = bool(bp.get("gpu_prune_kernel", False))
         insert_kernel = bool(bp.get("gpu_insert_kernel", False))
+        csr_kernel = bool(bp.get("gpu_csr_kernel", False))
         use_gpu = data.shape[0] >= thr and _lib.device_count() > 0
         if not use_gpu and m_low <= 0:
             return build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
@@ -168,6 +172,7 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
         if use_gpu:
             x = torch.from_numpy(np.ascontiguousarray(data)).to(torch.device("cuda", int(bp.get("device", 0))))
             g = build_graph_gpu(x, metric, M=self.M, ef_construction=self.efConstruction, selector=selector, linker=linker, search=search,
+                                **({"assembler": "kernel"} if csr_kernel else {}),  # (absent: build_graph_gpu's default, numpy on the host)
                                 **({"inserter": "kernel"} if insert_kernel else {}))  # (absent: build_graph_gpu's default, the torch ops)
         else:
             x = torch.from_numpy(np.ascontiguousarray(data))
@@ -177,6 +182,8 @@ class Mi355xBuilder(LeannBackendBuilderInterface):
             g = build_hnsw(data, metric, M=self.M, ef_construction=self.efConstruction)
         if m_low > 0:
             kw = {"pruner": "kernel"} if prune_kernel else {}  # (absent: prune_preserving_hubs' default, the host form)
+            if csr_kernel:
+                kw["assembler"] = "kernel"
             g = prune_preserving_hubs(g, x, self.M, m_low, float(bp.get("hub_fraction", 0.02)), selector=selector, linker=linker, **kw)
         return g
 

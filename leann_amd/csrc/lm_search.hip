@@ -1349,4 +1349,5 @@ int lm_topk_merge(const int64_t* d_in_ids, const float* d_in_dist, int32_t S, in
 #include "lm_prune_impl.h"
 #include "lm_insert_impl.h"
 #include "lm_wide_impl.h"
+#include "lm_csr_impl.h"
 

@@ -395,6 +395,112 @@ def _assemble_csr(levels_top: np.ndarray, graphs: "list[tuple[np.ndarray, np.nda
                    ef_construction=efc, cum_nneighbor_per_level=cum)
 
 
+ASSEMBLERS = ("numpy", "kernel")
+
+
+def _check_assembler(assembler: str) -> str:
+    if assembler not in ASSEMBLERS:
+        raise ValueError(f"assembler must be one of {ASSEMBLERS}, not {assembler!r}")
+    return assembler
+
+
+def _stream_of(t: torch.Tensor):
+    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else None
+
+
+def _level_array(levels):
+    """``levels`` -- one ``(nodes, adj)`` pair per level as Mi355xIndex.from_levels takes them: adj a contiguous int32 tensor
+    [n_rows, cap], nodes None (the identity) or a contiguous int32 tensor [n_rows] beside it -- as the host array of lm_graph_level."""
+    from . import _lib
+
+    arr = (_lib.GraphLevel * max(len(levels), 1))()
+    for l, (nodes, adj) in enumerate(levels):
+        if not (isinstance(adj, torch.Tensor) and adj.dtype == torch.int32 and adj.dim() == 2 and adj.is_contiguous()):
+            raise ValueError(f"levels[{l}]: adj must be a contiguous int32 tensor [n_rows, cap]")
+        if nodes is not None and not (isinstance(nodes, torch.Tensor) and nodes.dtype == torch.int32 and nodes.dim() == 1 and nodes.is_contiguous()
+                                      and nodes.shape[0] == adj.shape[0] and nodes.device == adj.device):
+            raise ValueError(f"levels[{l}]: nodes must be None or a contiguous int32 tensor [n_rows] beside adj")
+        arr[l] = _lib.GraphLevel(None if nodes is None or nodes.shape[0] == 0 else nodes.data_ptr(), None if adj.shape[0] == 0 else adj.data_ptr(),
+                                 adj.shape[0], adj.shape[1])
+    return arr
+
+
+@torch.no_grad()
+def levels_to_csr_kernel(levels, ntotal: int):
+    """The level adjacencies ``levels`` (see _level_array; level 0 first, the identity level) as the four CSR arrays, on the levels' device
+    and by the library alone (lm_graph_levels_to_csr_count, one synchronisation for the two sizes, then lm_graph_levels_to_csr_fill):
+    -> (levels int32 [n], node_offsets int64 [n + 1], level_ptr int64 [n_level_ptr], neighbors int32 [n_neighbors]); the two offset arrays
+    hold the library's uint64 values (torch has no arithmetic on uint64: view them as such on the host)."""
+    import ctypes as C
+
+    from . import _lib
+
+    lib = _lib.load()
+    n = int(ntotal)
+    arr = _level_array(levels)
+    dev = levels[0][1].device
+    stream = _stream_of(levels[0][1])
+    lv = torch.empty((n,), dtype=torch.int32, device=dev)
+    no = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    need = int(lib.lm_graph_levels_to_csr_workspace_bytes(n, arr, len(levels)))
+    ws = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+    nptr, nnb = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.lm_graph_levels_to_csr_count(n, arr, len(levels), lv.data_ptr(), no.data_ptr(), ws.data_ptr(), ws.numel(), C.byref(nptr), C.byref(nnb), stream),
+               "lm_graph_levels_to_csr_count")
+    lp = torch.empty((max(nptr.value, 1),), dtype=torch.int64, device=dev)  # (at least one element: an empty tensor has no address)
+    nb = torch.empty((max(nnb.value, 1),), dtype=torch.int32, device=dev)
+    _lib.check(lib.lm_graph_levels_to_csr_fill(n, arr, len(levels), lv.data_ptr(), no.data_ptr(), lp.data_ptr(), nb.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+               "lm_graph_levels_to_csr_fill")
+    return lv, no, lp[: nptr.value], nb[: nnb.value]
+
+
+@torch.no_grad()
+def assemble_csr_kernel(levels, ntotal: int, d: int, mt: int, entry: int, M: int, efc: int) -> HnswCsr:
+    """_assemble_csr's graph (base_sub = the identity) from device-resident levels through levels_to_csr_kernel: the four arrays are
+    copied to the host once, at the end, as HnswCsr holds them."""
+    n = int(ntotal)
+    if n == 0:
+        return HnswCsr(d=d, ntotal=0, metric_type=mt, levels=np.zeros(0, np.int32), level_ptr=np.zeros(0, np.uint64),
+                       node_offsets=np.zeros(1, np.uint64), neighbors=np.zeros(0, np.int32), entry_point=-1, max_level=-1)
+    lv, no, lp, nb = (t.cpu().numpy() for t in levels_to_csr_kernel(levels, n))
+    max_level = int(lv.max()) - 1
+    cum = np.array([0, 2 * M] + [2 * M + M * (i + 1) for i in range(max(max_level, 0) + 1)], dtype=np.int32)
+    return HnswCsr(d=d, ntotal=n, metric_type=mt, levels=lv, level_ptr=lp.view(np.uint64), node_offsets=no.view(np.uint64), neighbors=nb,
+                   entry_point=int(entry), max_level=max_level, ef_construction=efc, cum_nneighbor_per_level=cum)
+
+
+@torch.no_grad()
+def level_from_csr_kernel(levels: torch.Tensor, node_offsets: torch.Tensor, level_ptr: torch.Tensor, neighbors: torch.Tensor, level: int, cap: int,
+                          nodes: Optional[torch.Tensor] = None):
+    """One level of a CSR whose arrays are on the device (int32 levels / neighbors, the offsets as int64 tensors holding the uint64
+    values) in the fixed-capacity layout (lm_graph_csr_to_level): -> (adj int32 [n_rows, cap], -1 behind the list; deg int32 [n_rows];
+    overflow: a one-element int64 tensor, the entries that did not fit).  ``nodes``: the rows' node ids (int32, ascending), None = every
+    node."""
+    from . import _lib
+
+    lib = _lib.load()
+    n = levels.shape[0]
+    dev = levels.device
+    n_rows = n if nodes is None else nodes.shape[0]
+    adj = torch.empty((n_rows, int(cap)), dtype=torch.int32, device=dev)
+    deg = torch.empty((n_rows,), dtype=torch.int32, device=dev)
+    over = torch.zeros((1,), dtype=torch.int64, device=dev)
+    if n_rows == 0:
+        return adj, deg, over
+    ptr =lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    rc = lib.lm_graph_csr_to_level(n, node_offsets.data_ptr(), ptr(level_ptr), level_ptr.shape[0], ptr(neighbors), neighbors.shape[0], ptr(levels), int(level),
+                                   ptr(nodes), n_rows, int(cap), ptr(adj), ptr(deg), over.data_ptr(), _stream_of(levels))
+    _lib.check(rc, "lm_graph_csr_to_level")
+    return adj, deg, over
+
+
+def _csr_to_device(g: HnswCsr, dev):
+    """g's four arrays as device tensors, as level_from_csr_kernel takes them."""
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(dev)  # noqa: E731
+    return up(g.levels.astype(np.int32, copy=False), np.int32), up(g.node_offsets.astype(np.uint64, copy=False), np.int64), \
+        up(g.level_ptr.astype(np.uint64, copy=False), np.int64), up(g.neighbors.astype(np.int32, copy=False), np.int32)
+
+
 SEARCHES = ("csr", "view")
 INSERTERS = ("torch", "kernel")
 
@@ -494,7 +600,7 @@ def hip_search_fn(device_index: int = 0, beam: int = 2) -> SearchFn:
 def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_construction: int = 200, seed: int = 12345,
                     search_fn: Optional[SearchFn] = None, growth: float = 1.5, k_cand: int = 0,
                     seed_nodes: int = 2048, refine: bool = True, verbose: bool = False, alpha: float = 1.0, selector: str = "torch",
-                    linker: str = "torch", search: str = "csr", inserter: str = "torch") -> HnswCsr:
+                    linker: str = "torch", search: str = "csr", inserter: str = "torch", assembler: str = "numpy") -> HnswCsr:
     """x: [N, D] float tensor on the build device.  Returns the compact-CSR HNSW graph (host).  ``alpha`` > 1 relaxes the neighbour
     selection the way Vamana does (denser lists with longer edges: what a PQ-guided walk over a flat graph needs at 10M nodes -- DESIGN 8;
     inner-product metrics then assume unit vectors); 1.0 = the HNSW rule, the graphs every measurement so far was taken on.
@@ -510,9 +616,15 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
     ``inserter``: "torch" (default) = the step between the kernels (candidate merge and dedupe in refinement, keep mask -> edge lists,
     row clearing) by torch ops, with a host synchronisation per boolean-mask indexing and one ``inserted.sum()`` per batch; "kernel" =
     every insert batch and every refinement step is ONE lm_graph_insert_batch call on the level's view, and the number of inserted
-    nodes is counted on the host.  It needs selector="kernel", linker="kernel" and search="view", and builds the same graph byte for byte."""
+    nodes is counted on the host.  It needs selector="kernel", linker="kernel" and search="view", and builds the same graph byte for byte.
+    ``assembler``: "numpy" (default) = the final CSR is assembled on the host from an export of every level (_assemble_csr); "kernel" =
+    on the device, from the level adjacencies where they are (lm_graph_levels_to_csr_count / _fill), and the four arrays come to the
+    host once.  It needs search="view" (the int32 adjacencies), and returns the same arrays byte for byte."""
     select = _selector_fn(selector)
     _check_linker(linker)
+    _check_assembler(assembler)
+    if assembler == "kernel" and search != "view":
+        raise ValueError('assembler="kernel" needs search="view": lm_graph_levels_to_csr reads the int32 level adjacencies of the view build')
     if search not in SEARCHES:
         raise ValueError(f"search must be one of {SEARCHES}, not {search!r}")
     if search == "view" and linker != "kernel":
@@ -670,7 +782,15 @@ def build_graph_gpu(x: torch.Tensor, metric: str = "mips", M: int = 32, ef_const
         finished.insert(0, G)
 
     # final assembly over all nodes (level 0 subset == everything)
-    graphs = [(f.sub.cpu().numpy(), f.export()) for f in finished]
+    if assembler == "kernel":
+        levels = [(None, finished[0].adj)]
+        for f in finished[1:]:  # the upper levels' ids are local to their own node lists (they are small): to global ids, once
+            m = f.adj >= 0
+            a = torch.full_like(f.adj, -1)
+            a[m] = f.sub[f.adj[m].to(torch.int64)].to(torch.int32)
+            levels.append((f.sub.to(torch.int32).contiguous(), a.contiguous()))
+        return assemble_csr_kernel(levels, n, d, mt, entry_global, M, ef_construction)
+    graphs =[(f.sub.cpu().numpy(), f.export()) for f in finished]
     all_ids = np.arange(n, dtype=np.int64)
     return _assemble_csr(lv_np, graphs, all_ids, d, mt, entry_global, M, ef_construction)
 
@@ -743,7 +863,7 @@ def _with_level0(g: HnswCsr, new0: np.ndarray) -> HnswCsr:
 
 @torch.no_grad()
 def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_fraction: float = 0.02, selector: str = "torch",
-                          linker: str = "torch", pruner: str = "torch", return_hubs: bool = False):
+                          linker: str = "torch", pruner: str = "torch", return_hubs: bool = False, assembler: str = "numpy"):
     """High-degree-preserving pruning of the level-0 graph (LEANN paper, Algorithm 3, p. 6): storage drops from ~2M links per node
     to ~m_low while the few hub nodes that most searches pass through keep their full lists.
 
@@ -762,9 +882,14 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
     torch link weights, add_links in chunks).  "kernel": one call of lm_graph_prune_hubs on the device (prune_level0_kernel): hubs under
     the total order (in-degree descending, id ascending), canonical fp32 link weights, one link insertion -- the canonical rule whatever
     ``selector`` and ``linker`` say --; the level-0 lists go up as an int32 [n, 2M] array.  ``return_hubs``: return (graph, hubs) -- the
-    hub ids as an int64 numpy array (``pruner="kernel"``: in the contract's order; an empty array when nothing was pruned)."""
+    hub ids as an int64 numpy array (``pruner="kernel"``: in the contract's order; an empty array when nothing was pruned).
+    ``assembler``: "numpy" (default): the level-0 rows go up as a dense array built on the host and the pruned rows come back into the CSR
+    on the host (_with_level0).  "kernel" (with ``pruner="kernel"``; ignored by the host form): the CSR's arrays go up as they are, the
+    rows of every level come from lm_graph_csr_to_level and the pruned graph comes back through lm_graph_levels_to_csr_count / _fill: the
+    same graph byte for byte."""
     _selector_fn(selector)
     _check_linker(linker)
+    _check_assembler(assembler)
     if pruner not in PRUNERS:
         raise ValueError(f"pruner must be one of {PRUNERS}, not {pruner!r}")
     n = g.ntotal
@@ -772,6 +897,24 @@ def prune_preserving_hubs(g: HnswCsr, x: torch.Tensor, M: int, m_low: int, hub_f
         return (g, np.zeros(0, np.int64)) if return_hubs else g
     dev = x.device
     mt = g.metric_type
+    if pruner == "kernel" and assembler == "kernel":
+        nh = max(1, int(round(hub_fraction * n)))
+        lens = np.diff(g.level_ptr.astype(np.int64), append=np.int64(g.neighbors.shape[0]))
+        lens[g.node_offsets[:-1].astype(np.int64)] = 0
+        cap_up = max(M, int(lens.max()))  # an upper list keeps every entry, as _with_level0 copies it
+        lv_d, no_d, lp_d, nb_d = _csr_to_device(g, dev)
+        adj32, _, _ = level_from_csr_kernel(lv_d, no_d, lp_d, nb_d, 0, 2 * M)
+        new32, _, _, hubs_d = prune_level0_kernel(_padded_table(x), adj32, m_low, nh, mt)
+        levels = [(None, new32)]
+        for l in range(1, g.max_level + 1):
+            nodes = torch.nonzero(lv_d > l).flatten().to(torch.int32)
+            levels.append((nodes, level_from_csr_kernel(lv_d, no_d, lp_d, nb_d, l, cap_up, nodes)[0]))
+        lv, no, lp, nb = (t.cpu().numpy() for t in levels_to_csr_kernel(levels, n))
+        out = HnswCsr(d=g.d, ntotal=n, metric_type=mt, levels=lv, level_ptr=lp.view(np.uint64), node_offsets=no.view(np.uint64), neighbors=nb,
+                      entry_point=g.entry_point, max_level=g.max_level, ef_construction=g.ef_construction,
+                      cum_nneighbor_per_level=g.cum_nneighbor_per_level)
+        out.validate()
+        return (out, hubs_d.cpu().numpy().astype(np.int64)) if return_hubs else out
     p0 = g.node_offsets[:-1].astype(np.int64)
     beg = g.level_ptr[p0].astype(np.int64)
     deg = (g.level_ptr[p0 + 1].astype(np.int64) - beg)

@@ -95,6 +95,18 @@ class Mi355xIndex:
         idx._levels_keepalive = keep
         return idx
 
+    def to_csr(self, M: int = 0, ef_construction: int = 200) -> HnswCsr:
+        """A view handle's graph (from_levels) as it stands, as the compact CSR that from_csr opens and write_index stores: assembled on
+        the device from the level tensors (lm_graph_levels_to_csr_count / _fill), copied to the host once.  ``M`` and
+        ``ef_construction`` are the build parameters recorded in the result (M = 0: half the level-0 capacity)."""
+        levels = getattr(self, "_levels_keepalive", None)
+        if not levels:
+            raise ValueError("to_csr needs a view handle (Mi355xIndex.from_levels)")
+        from .gpu_graph_build import assemble_csr_kernel
+
+        i = self.info
+        return assemble_csr_kernel(levels, i.ntotal, i.d, i.metric, i.entry_point, int(M) or max(levels[0][1].shape[1] // 2, 1), int(ef_construction))
+
     @classmethod
     def read(cls, path: str, device: int = 0) -> "Mi355xIndex":
         """faiss.read_index(path, IO_FLAG_MMAP, HNSWIndexConfig) equivalent (hnsw_backend.py:145-151)."""
